@@ -7,11 +7,14 @@ bookkeeping) runs on the device as one HIP graph.  Inputs (weights, cache, first
 timed region starts.  Rank 0 prints ONE JSON line.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--model llama2-7b|llama2-70b|mixtral-8x7b|tinyllama|tiny]
-                  [--recipe 4.0bpw|3.5bpw|2.5bpw|gptq-4bit-128g] [--ctx C] [--batch B] [--cache fp16|q4] [--no-cpu-baseline]
-                  [--no-prefill] [--no-parity-check] [--no-ctx-window] [--no-graph] [--parallel pipeline|tp]
-  python bench.py --cpu-baseline-only [--model ...] [--recipe ...]     (what the main run starts as a child for `cpu_baseline`)
+                  [--recipe 4.0bpw|3.5bpw|2.5bpw|gptq-4bit-128g] [--ctx C] [--batch B] [--cache fp16|q4] [--no-graph]
+                  [--parallel pipeline|tp] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-prefill] [--no-parity-check] [--no-ctx-window] [--no-dropin]]
+  python bench.py --cpu-baseline-only [--model ...] [--recipe ...]     (what a --full run starts as a child for `cpu_baseline`)
 
-Beside the headline value the line carries `roofline` (q_gemm launches: algorithmic bytes / HIP-event time per launch against
+A plain run sets up, runs a clock ramp and W warm-up steps, times exactly K steps (one window) and prints the line;
+`--dump-outputs DIR` writes the timed steps' outputs (logits.npy, tokens.npy) right after the timing.  Everything else is
+behind `--full`: 5 timed windows (median reported) and beside the headline value `roofline` (q_gemm launches: algorithmic bytes / HIP-event time per launch against
 8 TB/s), `parity_check` (device logits vs the oracle on the first two layers + head of the timed checkpoint, before timing),
 `extra.ctx1920_tokens_per_s` (SURVEY.md 8d's second window), `prefill` (BASELINE configs[2]: 8 x 2048 tokens on the native
 kernels) and `cpu_baseline` (the oracle "port" on the host cores: variant B unsampled fp32 GEMV pass, variant A the C port
@@ -58,12 +61,24 @@ def parse():
     p.add_argument("--batch", type=int, default=1, help="sequences decoded together (BASELINE configs[4]: 16)")
     p.add_argument("--parallel", default="pipeline", choices=["pipeline", "tp"],
                    help="N > 1: layer-split pipeline (default, weak scaling) or tensor parallel (column shards + all-gather, strong scaling)")
-    p.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps (each after --warmup untimed steps from the same "
-                                                           "cache position); the MEDIAN window is the reported value")
+    p.add_argument("--windows", type=int, default=None, help="timed windows of --steps steps (each after --warmup untimed steps from the same "
+                                                              "cache position); the MEDIAN window is the reported value (default: 1, "
+                                                              "with --full 5)")
     p.add_argument("--headline-only", action="store_true", help="= --no-cpu-baseline --no-prefill --no-dropin --no-ctx-window (A/B runs)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline: the oracle parity check before timing, 5 timed windows, the q_gemm roofline, "
+                        "the ctx-1920 window, prefill, the drop-in figure and the CPU baseline (each --no-* flag still drops its part). "
+                        "Without it a run sets up, warms up, times --steps steps once and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what they computed as DIR/<name>.npy (float32 / float64): logits.npy = the "
+                        "last step's logits [batch, vocab], tokens.npy = the tokens of the timed steps [batch, steps]")
     a = p.parse_args()
-    if a.headline_only:
+    if a.headline_only or not a.full:
         a.no_cpu_baseline = a.no_prefill = a.no_dropin = a.no_ctx_window = True
+    if not a.full:
+        a.no_parity_check = True
+    if a.windows is None:
+        a.windows = 5 if a.full else 1
     return a
 
 
@@ -619,7 +634,7 @@ def cpu_baseline_in_child(args, timeout_s: int = 420):
     """Runs `bench.py --cpu-baseline-only` as a child process and returns its JSON object: the baseline allocates tens of GB
     of host memory and runs for tens of seconds -- a kill or a hang there must not cost the GPU line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--model", args.model, "--recipe", args.recipe]
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--cpu-baseline-only", "--model", args.model, "--recipe", args.recipe]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s, cwd=ROOT)
         lines = [l for l in r.stdout.strip().splitlines() if l.startswith("{")]
@@ -723,6 +738,19 @@ def prefill_rate(model_name: str, recipe: str, device: str, batch: int = 8, seq:
     return out
 
 
+def dump_outputs(path: str, dec, cfg, toks, max_bytes: int = 32 << 20) -> None:
+    """--dump-outputs: what the timed decode hands its caller, read back after the timing -- the last step's logits (fp16 on the
+    device, written as float32) and the greedy tokens of the timed steps (int32 on the device, written as float64: exact).  The
+    tokens are capped at `max_bytes` (the most recent steps kept); the logits of one step are at most a few MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    logits = dec.logits[:, :cfg.vocab_size].float().cpu().numpy().astype(np.float32)
+    tokens = toks.cpu().numpy().astype(np.float64)
+    keep = max(1, max_bytes // (8 * tokens.shape[0]))
+    np.save(os.path.join(path, "logits.npy"), logits)
+    np.save(os.path.join(path, "tokens.npy"), tokens[:, -keep:])
+
+
 def spawn_ranks(n: int) -> None:
     """Re-executes this command under `python -m torch.distributed.run --nnodes=1 --nproc-per-node n` on 127.0.0.1 (one rank per
     GPU over RCCL), after checking that n GPUs are there; the child's exit code is ours.  Fails loudly -- exit code 2 and one line
@@ -755,6 +783,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("[bench] --gpus must be >= 1")
+    if args.dump_outputs and args.gpus > 1:
+        raise SystemExit("[bench] --dump-outputs: one GPU only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` (the driver's N = 1 form with a larger N): start the N ranks ourselves, one per GPU, exactly as
         # the driver's own launcher line does -- never fall through to a one-GPU run that would print an n_gpus = 1 line
@@ -790,7 +820,7 @@ def main():
     elif n_gpus > 1:
         from exllamav2_amd.pipeline import run_layer_split_bench
         result = run_layer_split_bench(cfg, args, rank, world, device)
-        if os.environ.get("EXL2_BENCH_TP_LINE", "1") != "0" and not getattr(cfg, "num_experts", 0):
+        if args.full and os.environ.get("EXL2_BENCH_TP_LINE", "1") != "0" and not getattr(cfg, "num_experts", 0):
             # the second labelled figure of an N > 1 run: ONE sequence decoded by all ranks together (tensor parallel, strong
             # scaling) -- what a "bs=1 on N GPUs" reader expects; nested in the same JSON line (the contract is one line)
             try:
@@ -834,7 +864,7 @@ def main():
             dec.reset(torch.tensor([1] * args.batch), 0)
             dec.run(64, use_graph=not args.no_graph)
             torch.cuda.synchronize()
-        # `--windows` identical timed windows (default 5), each = W untimed warm-up steps then EXACTLY K timed steps between two
+        # `--windows` identical timed windows (default 1, with --full 5), each = W untimed warm-up steps then EXACTLY K timed steps between two
         # device synchronisations, from the same cache position; the reported value is the MEDIAN window (20 steps are 28 ms of
         # work: one window is inside box noise), every window's rate is printed beside it
         window_dt = []
@@ -852,9 +882,11 @@ def main():
         toks = dec.tokens(args.ctx + args.warmup, args.steps)
         assert int(dec.cache_seqlens[0]) == args.ctx + args.warmup + args.steps
         assert int(toks.min()) >= 0 and int(toks.max()) < cfg.vocab_size
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dec, cfg, toks)
 
-        if getattr(cfg, "num_experts", 0) or args.batch != 1:
-            # MoE / batched runs: headline rate only (the q_gemm roofline figure is defined on configs[1])
+        if not args.full or getattr(cfg, "num_experts", 0) or args.batch != 1:
+            # plain runs, MoE / batched runs: headline rate only (the q_gemm roofline figure is defined on configs[1])
             result = {"value": args.batch * args.steps / dt, "ms_per_step": dt / args.steps * 1e3, "load_s": t_load, "windows": windows}
             if parity is not None: result["parity_check"] = parity
             dec.free()

@@ -69,7 +69,7 @@ def test_bench_cpu_baseline_child_prints_one_json_object_with_both_variants():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--cpu-baseline-only", "--model", "tiny"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--cpu-baseline-only", "--model", "tiny"],
                        capture_output=True, text=True, timeout=300, cwd=root)
     assert r.returncode == 0, r.stderr[-400:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@
 # STAGES (any subset, in this order):
 #   smoke      __graft_entry__.smoke()
 #   tests      pytest -m gpu            (TESTS="tests/test_x.py -k expr" narrows it; default: all of tests/)
-#   bench      bench.py with default flags + with the driver's flags (--gpus 1 --steps 20 --warmup 5); bench_default / bench_driver: one of them
+#   bench      bench.py --full (every figure of the line) + the plain headline run (--gpus 1 --steps 20 --warmup 5); bench_default / bench_driver: one of them
 #   stats      rocprofv3 --kernel-trace --stats of the headline decode loop  -> ${TAG}_kernel_stats.csv
 #   pmc        rocprofv3 --pmc FETCH_SIZE (own pass, kernel-trace only) over the headline loop, graph replay first and eager
 #              launches if that does not finish -> ${TAG}_pmc_summary.json
@@ -22,7 +22,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; R=$ROOT/gpurun_out; 
 STAGES=${STAGES:-"smoke tests bench"}
 cd $ROOT
 has() { case " $STAGES " in *" $1 "*) return 0;; esac; return 1; }
-line() { timeout -k 10 ${2:-300} python bench.py $1 2>$R/${T}_last.err | tail -1; }
+line() { timeout -k 10 ${2:-300} python bench.py --full $1 2>$R/${T}_last.err | tail -1; }
 
 if has smoke; then echo "== smoke"; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $R/${T}_smoke.log 2>&1; echo "rc=$?"; tail -1 $R/${T}_smoke.log; fi
 if has tests; then
@@ -30,14 +30,14 @@ if has tests; then
   timeout -k 10 ${TESTS_TIMEOUT:-1200} python -m pytest ${TESTS:-tests} -m gpu -q --timeout 600 ${TESTS_X--x} > $R/${T}_pytest_gpu.log 2>&1; echo "rc=$?"; tail -${TESTS_TAIL:-4} $R/${T}_pytest_gpu.log
 fi
 if has bench || has bench_default; then
-  echo "== bench (default flags)"; timeout -k 10 900 python bench.py > $R/${T}_bench.json 2> $R/${T}_bench.err; echo "rc=$?"; cut -c1-1800 $R/${T}_bench.json; tail -3 $R/${T}_bench.err
+  echo "== bench --full"; timeout -k 10 900 python bench.py --full > $R/${T}_bench.json 2> $R/${T}_bench.err; echo "rc=$?"; cut -c1-1800 $R/${T}_bench.json; tail -3 $R/${T}_bench.err
 fi
 if has bench || has bench_driver; then
   echo "== bench (the driver's flags)"; timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $R/${T}_bench_driver_flags.json 2>/dev/null; cut -c1-400 $R/${T}_bench_driver_flags.json
 fi
 if has stats; then
   echo "== rocprofv3 kernel stats (bs=1 headline loop)"
-  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_stats -o $T -- python $ROOT/bench.py --steps 64 --warmup 8 --windows 1 --headline-only --no-parity-check > $R/${T}_rocprof_stats.log 2>&1); echo "rc=$?"
+  (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/prof_stats -o $T -- python $ROOT/bench.py --full --steps 64 --warmup 8 --windows 1 --headline-only --no-parity-check > $R/${T}_rocprof_stats.log 2>&1); echo "rc=$?"
   f=$(find $R/prof_stats -name "${T}_kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $R/${T}_kernel_stats.csv && head -8 $f | cut -c1-170
   rm -rf $R/prof_stats
 fi
@@ -45,7 +45,7 @@ if has pmc; then
   for mode in graph nograph; do
     flag=""; [ $mode = nograph ] && flag="--no-graph"
     echo "== rocprofv3 --pmc FETCH_SIZE ($mode)"
-    (cd /tmp && EXL2_BENCH_RAMP_S=0 timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/prof_pmc -o $T -- python $ROOT/bench.py --steps ${PMC_STEPS:-4} --warmup 1 --windows 1 --headline-only $flag --no-parity-check > $R/${T}_rocprof_pmc_$mode.log 2>&1); rc=$?; echo "rc=$rc"
+    (cd /tmp && EXL2_BENCH_RAMP_S=0 timeout -k 10 ${PMC_TIMEOUT:-240} rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $R/prof_pmc -o $T -- python $ROOT/bench.py --full --steps ${PMC_STEPS:-4} --warmup 1 --windows 1 --headline-only $flag --no-parity-check > $R/${T}_rocprof_pmc_$mode.log 2>&1); rc=$?; echo "rc=$rc"
     python - $mode $T <<'PY'
 import csv, glob, collections, json, sys
 mode, tag = sys.argv[1], sys.argv[2]
@@ -94,7 +94,7 @@ if has ab; then
   for rep in $(seq 1 ${REPS:-2}); do
     for v in ${VARIANTS:-head}; do
       name=${v%%=*}; envs=""; [ "$name" != "$v" ] && envs=$(echo "${v#*=}" | tr ',' ' ')
-      echo -n "$name : "; env $envs timeout -k 10 300 python bench.py --steps ${AB_STEPS:-256} --warmup 16 --headline-only --no-parity-check $AB_FLAGS 2>/dev/null | python -c "
+      echo -n "$name : "; env $envs timeout -k 10 300 python bench.py --full --steps ${AB_STEPS:-256} --warmup 16 --headline-only --no-parity-check $AB_FLAGS 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); r = d.get('roofline', {})
 print(d['value'], 'tok/s', d.get('windows', {}).get('tokens_per_s'), r.get('avg_launch_us'), 'us/launch', r.get('frac'))"
