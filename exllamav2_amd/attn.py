@@ -1,6 +1,7 @@
 """ExLlamaV2Attention (reference attn.py:241-330 load/make_q_attn, :1017-1196 forward, :466-638 forward_paged)."""
 from __future__ import annotations
 
+import functools
 import os
 
 import torch
@@ -27,6 +28,15 @@ class ExLlamaV2Attention:
         self.q4_two_launches = os.environ.get("EXL2_Q4_LAUNCHES", "1") != "4"
         # ... or ONE (RoPE + pack + attention + merge: csrc/attn_q4.hip, the FUSED form; head_dim 128) -- EXL2_Q4_LAUNCHES=2 keeps two
         self.q4_one_launch = os.environ.get("EXL2_Q4_LAUNCHES", "1") == "1"
+
+    def _q_entries(self, wbits: int):
+        """(one-launch step, RoPE + pack, attention from the codes) of a quantized cache: the Q4 mirrors, or the width-carrying ones
+        bound to 6 / 8 bits -- same kernels (csrc/attn_q4.hip, csrc/cache_q.hip), same switches"""
+        ext = self.ext
+        if wbits == 4:
+            return ext.attn_q4_decode_fused, ext.rope_quant_append_q4, ext.paged_attn_q4
+        return (functools.partial(ext.attn_q_decode_fused, wbits=wbits), functools.partial(ext.rope_quant_append_q, wbits=wbits),
+                functools.partial(ext.paged_attn_q, wbits=wbits))
 
     def load(self, ck: dict):
         cfg, m = self.model.config, self.model
@@ -72,7 +82,7 @@ class ExLlamaV2Attention:
         return q, k, v
 
     def _attend(self, q, k, v, cache, past_len, cache_seqlens, block_table):
-        """RoPE(q, new k) + KV append + attention over the (paged or contiguous, FP16 or Q4) cache -> attn_out rows."""
+        """RoPE(q, new k) + KV append + attention over the (paged or contiguous, FP16 or Q4 / Q6 / Q8) cache -> attn_out rows."""
         cfg, m, ext = self.model.config, self.model, self.ext
         b, q_len = q.shape[0], q.shape[1]
         rows = b * q_len
@@ -80,10 +90,11 @@ class ExLlamaV2Attention:
         if cache is None:
             raise RuntimeError("ExLlamaV2Attention.forward: a cache is required")
         attn_out = m.temp_attn[:rows].view(b, q_len, cfg.num_attention_heads, cfg.head_dim)
-        # Q4 cache, decode-sized step: attend straight from the codes (attn_q4.hip) -- the reference unpacks the whole live
+        # quantized cache (Q4 / Q6 / Q8), decode-sized step: attend straight from the codes (attn_q4.hip) -- the reference unpacks the whole live
         # range to an fp16 temp for every layer of every step (cache.py:472-514)
         # (the step's own K/V are attended in fp16 and quantised afterwards, the reference's order)
-        q4_direct = (getattr(cache, "wbits", 0) == 4 and hasattr(cache, "q4_views") and self.q4_fused and q_len <= 8
+        wbits = getattr(cache, "wbits", 0)
+        q4_direct = (wbits in (4, 6, 8) and hasattr(cache, "q4_views") and self.q4_fused and q_len <= 8
                      and q_len * (cfg.num_attention_heads // cfg.num_key_value_heads) <= 64
                      and cfg.head_dim in (64, 128, 256)
                      and (cfg.num_key_value_heads * cfg.head_dim) % 512 == 0)     # codec blocks (512 elements) must not span tokens
@@ -102,21 +113,22 @@ class ExLlamaV2Attention:
             # new K/V -> (rotated) into the fp16 staging rows -> quantised into the cache -> attention over codes
             kq, ks, vq, vs = cache.q4_views(self.layer_idx, paged)
             two = getattr(self, "q4_two_launches", False)
-            if getattr(self, "q4_one_launch", False) and ext.attn_q4_decode_fused(
+            one_launch, rope_pack, attn_codes = self._q_entries(wbits)
+            if getattr(self, "q4_one_launch", False) and one_launch(
                     q, k, v, kq, ks, vq, vs, attn_out, m.sin, m.cos, sl, bt, past, cfg.rope_style, m.attn_scratch, m.attn_counters):
                 return attn_out
-            if not (two and ext.rope_quant_append_q4(q, k, v, kq, ks, vq, vs, m.sin, m.cos, past if not paged else 0,
-                                                     sl if paged else none_tensor, bt if paged else none_tensor, cfg.rope_style)):
+            if not (two and rope_pack(q, k, v, kq, ks, vq, vs, m.sin, m.cos, past if not paged else 0,
+                                      sl if paged else none_tensor, bt if paged else none_tensor, cfg.rope_style)):
                 ext.rope_kv_append(q, k, v, kc, vc, m.sin, m.cos, past if not paged else 0,
                                    sl if paged else none_tensor, bt if paged else none_tensor, cfg.rope_style)
                 if paged:
                     cache.store_kv_state(self.layer_idx, b, 0, q_len, 256, cache_seqlens, block_table)
                 else:
                     cache.store_kv_state(self.layer_idx, b, past_len, q_len)
-            ok = ext.paged_attn_q4(q, kq, ks, vq, vs, attn_out, sl, bt, len_const=past, len_offset=q_len,
-                                   scratch=m.attn_scratch, k_new=k, v_new=v, counters=m.attn_counters if two else None)
+            ok = attn_codes(q, kq, ks, vq, vs, attn_out, sl, bt, len_const=past, len_offset=q_len,
+                            scratch=m.attn_scratch, k_new=k, v_new=v, counters=m.attn_counters if two else None)
             if not ok:
-                raise RuntimeError("ExLlamaV2Attention: fused Q4 attention rejected a shape it was selected for")
+                raise RuntimeError("ExLlamaV2Attention: attention from the cache's codes rejected a shape it was selected for")
         else:
             # decode-shaped steps: one launch does RoPE + append + attention + split merge; otherwise three launches
             fused = self.fused_decode and ext.attn_decode_fused(
@@ -134,15 +146,16 @@ class ExLlamaV2Attention:
         return attn_out
 
     def q4_chain_capable(self, cache) -> bool:
-        """the chained step can attend straight from this Q4 cache's codes (the conditions of _attend's q4_direct at q_len 1)"""
+        """the chained step can attend straight from this quantized cache's codes (Q4 / Q6 / Q8; the conditions of _attend's
+        q4_direct at q_len 1)"""
         cfg = self.model.config
-        return (getattr(cache, "wbits", 0) == 4 and hasattr(cache, "q4_views") and self.q4_fused
+        return (getattr(cache, "wbits", 0) in (4, 6, 8) and hasattr(cache, "q4_views") and self.q4_fused
                 and cfg.num_attention_heads // cfg.num_key_value_heads <= 64 and cfg.head_dim in (64, 128, 256)
                 and (cfg.num_key_value_heads * cfg.head_dim) % 512 == 0)
 
     def attend_chain(self, q, k, v, cache, cache_seqlens, block_table, out_invperm):
         """Decode attention of the chained step (model.GreedyGraphDecoder), output written in o_proj's packed order.  Paged
-        FP16 cache: the one-launch kernel.  Paged Q4 cache: RoPE + Q4 pack of the new rows (csrc/cache_q.hip: rope_quant_q4_kernel),
+        FP16 cache: the one-launch kernel.  Paged Q4 / Q6 / Q8 cache: RoPE + pack of the new rows (csrc/cache_q.hip: rope_quant_q4_kernel),
         attention straight from the codes with the split merge inside (csrc/attn_q4.hip) -- the two launches of _attend's q4_direct route.  Raises when
         the shape needs another path (the decoder then un-chains)."""
         cfg, m, ext = self.model.config, self.model, self.ext
@@ -153,17 +166,18 @@ class ExLlamaV2Attention:
             attn_out = m.temp_attn[:b * q_len].view(b, q_len, cfg.num_attention_heads, cfg.head_dim)
             kq, ks, vq, vs = cache.q4_views(self.layer_idx, True)
             two = getattr(self, "q4_two_launches", False)
-            if getattr(self, "q4_one_launch", False) and ext.attn_q4_decode_fused(
+            one_launch, rope_pack, attn_codes = self._q_entries(cache.wbits)
+            if getattr(self, "q4_one_launch", False) and one_launch(
                     q, k, v, kq, ks, vq, vs, attn_out, m.sin, m.cos, cache_seqlens, block_table, 0, cfg.rope_style, m.attn_scratch,
                     m.attn_counters, out_invperm=out_invperm):
                 return attn_out
-            if not (two and ext.rope_quant_append_q4(q, k, v, kq, ks, vq, vs, m.sin, m.cos, 0, cache_seqlens, block_table, cfg.rope_style)):
+            if not (two and rope_pack(q, k, v, kq, ks, vq, vs, m.sin, m.cos, 0, cache_seqlens, block_table, cfg.rope_style)):
                 kc, vc = cache.paged_view(self.layer_idx)
                 ext.rope_kv_append(q, k, v, kc, vc, m.sin, m.cos, 0, cache_seqlens, block_table, cfg.rope_style)
                 cache.store_kv_state(self.layer_idx, b, 0, q_len, 256, cache_seqlens, block_table)
-            if not ext.paged_attn_q4(q, kq, ks, vq, vs, attn_out, cache_seqlens, block_table, len_const=0, len_offset=q_len,
-                                     scratch=m.attn_scratch, k_new=k, v_new=v, out_invperm=out_invperm,
-                                     counters=m.attn_counters if two else None):
+            if not attn_codes(q, kq, ks, vq, vs, attn_out, cache_seqlens, block_table, len_const=0, len_offset=q_len,
+                              scratch=m.attn_scratch, k_new=k, v_new=v, out_invperm=out_invperm,
+                              counters=m.attn_counters if two else None):
                 raise RuntimeError("attend_chain: shape not covered by the Q4 attention kernel")
             return attn_out
         kc, vc = cache.paged_view(self.layer_idx)

@@ -1,4 +1,5 @@
-// attn_q4.hip -- decode attention straight from the Q4 KV cache.
+// attn_q4.hip -- decode attention straight from the quantized KV cache: Q4 and, with 8-bit codes on the key side
+// or on both, Q6 / Q8 (the text below speaks of Q4; what 8 bits change is at q_code_pairs).
 //
 // Reference behaviour: ExLlamaV2Cache_Q4.get_kv_state (cache.py:472-514) unpacks the WHOLE live range of K and V to an
 // fp16 temp for every layer of every decode step (q_to_fp16_kv, cache.cu:324-401), attention then reads that temp:
@@ -86,12 +87,48 @@ DEV f16x8 rope8_128(f16x8 own, f16x8 partner, int c, const f16* sr, const f16* c
     return y;
 }
 
-template <int HDIM, int RB, bool FUSED = false>
+// One side's codes of a lane and key: 16 elements = 8 bytes at 4 bits (two per byte, low nibble first), 16 bytes at 8 bits (element
+// order).  q_code_pairs turns them into the 8 half2 pairs (1024 + c_even, 1024 + c_odd) of elements (2 i, 2 i + 1): the byte lands
+// in the mantissa of 0x6400 (ulp 1 on [1024, 2048), so 8-bit codes are as exact as 4-bit ones).  Q_BIAS = what is taken off again
+// once per batch: 1024 + the code's own offset (8 | 128).
+template <int BITS> struct QCodes { typedef u32x2 T; };
+template <> struct QCodes<8> { typedef u32x4 T; };
+template <int BITS> constexpr float q_bias() { return BITS == 8 ? 1152.0f : 1032.0f; }
+
+template <int BITS>
+DEV void q_code_pairs(const typename QCodes<BITS>::T c, f16x2 (&d)[8])
+{
+    if constexpr (BITS == 4)
+    {
+        const u32 l0 = c.x & 0x0F0F0F0Fu, h0 = (c.x >> 4) & 0x0F0F0F0Fu;
+        const u32 l1 = c.y & 0x0F0F0F0Fu, h1 = (c.y >> 4) & 0x0F0F0F0Fu;
+        d[0] = as_h2(byte_perm(h0, l0, 0x0C040C00u) | 0x64006400u); d[1] = as_h2(byte_perm(h0, l0, 0x0C050C01u) | 0x64006400u);
+        d[2] = as_h2(byte_perm(h0, l0, 0x0C060C02u) | 0x64006400u); d[3] = as_h2(byte_perm(h0, l0, 0x0C070C03u) | 0x64006400u);
+        d[4] = as_h2(byte_perm(h1, l1, 0x0C040C00u) | 0x64006400u); d[5] = as_h2(byte_perm(h1, l1, 0x0C050C01u) | 0x64006400u);
+        d[6] = as_h2(byte_perm(h1, l1, 0x0C060C02u) | 0x64006400u); d[7] = as_h2(byte_perm(h1, l1, 0x0C070C03u) | 0x64006400u);
+    }
+    else
+    {
+        // one v_perm per pair: bytes (2 j, 2 j + 1) of a word into the low bytes of the two halves, 0x64 above them
+        const u32 w[4] = {c.x, c.y, c.z, c.w};
+        #pragma unroll
+        for (int j = 0; j < 4; j++)
+        {
+            d[2 * j]     = as_h2(byte_perm(0x64646464u, w[j], 0x04010400u));
+            d[2 * j + 1] = as_h2(byte_perm(0x64646464u, w[j], 0x04030402u));
+        }
+    }
+}
+
+// KBITS / VBITS: code width of the key / value side -- (4, 4) = Q4, (8, 4) = Q6, (8, 8) = Q8 (cache.cu:259-276).  One body: the
+// widths change how many bytes a lane loads per key (8 | 16), how they become half2 pairs and the bias -- nothing else.
+template <int HDIM, int RB, bool FUSED = false, int KBITS = 4, int VBITS = 4>
 KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4Args a)
 {
+    static_assert((KBITS == 4 || KBITS == 8) && (VBITS == 4 || VBITS == 8), "code widths: 4 or 8 bits");
     static_assert(!FUSED || HDIM == 128 || HDIM == 64, "the one-launch form is built for head_dim 128 and 64");
     DYN_SMEM(smem);
-    constexpr int LPK = HDIM / 16;              // lanes per key: 16 elements (8 code bytes) each
+    constexpr int LPK = HDIM / 16;              // lanes per key: 16 elements (8 code bytes at 4 bits, 16 at 8) each
     constexpr int KPW = 64 / LPK;
     constexpr int NSTREAM = AQ_WAVES * KPW;
     constexpr int ROWF = HDIM + 2;
@@ -135,13 +172,13 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
                 else tok = (size_t)b * a.page_size + pos;
                 const size_t cache_off = (tok * a.KVH + kh) * HDIM;
                 const size_t src = (((size_t)b * a.s + j) * a.KVH + kh) * HDIM;
-                if (is_v) q_pack_lane<4>(lane, ((const f16x2*)(a.v_new + src))[lane], (u8*)a.v_codes, (f16*)a.v_scales, cache_off);
+                if (is_v) q_pack_lane<VBITS>(lane, ((const f16x2*)(a.v_new + src))[lane], (u8*)a.v_codes, (f16*)a.v_scales, cache_off);
                 else
                 {
                     f16x2 w = ((const f16x2*)(a.k_new + src))[lane];
                     const int srow = pos > 0 ? pos : 0;
                     if (a.rope) w = rope_lane_pair<HDIM>(w, lane, a.sin + (size_t)srow * HDIM, a.cos + (size_t)srow * HDIM, a.neox != 0);
-                    q_pack_lane<4>(lane, w, (u8*)a.k_codes, (f16*)a.k_scales, cache_off);
+                    q_pack_lane<KBITS>(lane, w, (u8*)a.k_codes, (f16*)a.k_scales, cache_off);
                 }
             }
         }
@@ -223,13 +260,15 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
         for (int e = 0; e < 16; e++) o[r][e] = 0.0f;
     }
 
-    const size_t tok_codes = (size_t)a.KVH * (HDIM / 2);                // bytes per token slot
+    constexpr int KROW = HDIM * KBITS / 8, VROW = HDIM * VBITS / 8;      // code bytes of a head row
+    const size_t tok_kcodes = (size_t)a.KVH * KROW;                     // bytes per token slot
+    const size_t tok_vcodes = (size_t)a.KVH * VROW;
     const size_t tok_scales = (size_t)a.KVH * (HDIM / 32);
     const int past = a.k_new ? total - a.s : total;                      // keys [past, total) come from k_new / v_new
     const int k_old_end = min(k_end, past);
     // Codes stay biased: a pair is the half2 (1024 + c_even, 1024 + c_odd) straight from v_perm + or; the "- 8" is applied
     // once per batch through sum(qh) on the K side and through sum(p s) on the V side (fp32, exact enough: the biased
-    // sums are ~130x the centred ones, 2^-24 relative each).  The running maximum is updated once per batch of AQ_UNROLL
+    // sums are ~130x the centred ones, 2^-24 relative each; at 8 bits, "- 128": ~9x).  The running maximum is updated once per batch of AQ_UNROLL
     // steps, so the 16 accumulators are rescaled once per batch, not per key.
     constexpr int STEP = AQ_WAVES * KPW;
     float qsum[RB], osub[RB];
@@ -239,12 +278,13 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
         float t = 0.0f;
         #pragma unroll
         for (int i = 0; i < 8; i++) t += (float)qf[r][i].x + (float)qf[r][i].y;
-        qsum[r] = t * 1032.0f;
+        qsum[r] = t * q_bias<KBITS>();
         osub[r] = 0.0f;
     }
     for (int base0 = k_start + wv * KPW; base0 < k_old_end; base0 += AQ_UNROLL * STEP)
     {
-        u32x2 kcs[AQ_UNROLL], vcs[AQ_UNROLL];
+        typename QCodes<KBITS>::T kcs[AQ_UNROLL];
+        typename QCodes<VBITS>::T vcs[AQ_UNROLL];
         f16 kss[AQ_UNROLL], vss[AQ_UNROLL];
         #pragma unroll
         for (int un = 0; un < AQ_UNROLL; un++)
@@ -260,10 +300,11 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
             }
             else
                 tok = (size_t)b * a.page_size + kp;
-            const size_t co = tok * tok_codes + (size_t)kh * (HDIM / 2) + u * 8;
+            const size_t kco = tok * tok_kcodes + (size_t)kh * KROW + u * (2 * KBITS);
+            const size_t vco = tok * tok_vcodes + (size_t)kh * VROW + u * (2 * VBITS);
             const size_t so = tok * tok_scales + (size_t)kh * (HDIM / 32) + (u >> 1);
-            kcs[un] = ld_nt((const u32x2*)(a.k_codes + co));
-            vcs[un] = ld_nt((const u32x2*)(a.v_codes + co));
+            kcs[un] = ld_nt((const typename QCodes<KBITS>::T*)(a.k_codes + kco));
+            vcs[un] = ld_nt((const typename QCodes<VBITS>::T*)(a.v_codes + vco));
             kss[un] = a.k_scales[so];
             vss[un] = a.v_scales[so];
         }
@@ -272,13 +313,8 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
         #pragma unroll
         for (int un = 0; un < AQ_UNROLL; un++)
         {
-            const u32 l0 = kcs[un].x & 0x0F0F0F0Fu, h0 = (kcs[un].x >> 4) & 0x0F0F0F0Fu;
-            const u32 l1 = kcs[un].y & 0x0F0F0F0Fu, h1 = (kcs[un].y >> 4) & 0x0F0F0F0Fu;
             f16x2 kd[8];
-            kd[0] = as_h2(byte_perm(h0, l0, 0x0C040C00u) | 0x64006400u); kd[1] = as_h2(byte_perm(h0, l0, 0x0C050C01u) | 0x64006400u);
-            kd[2] = as_h2(byte_perm(h0, l0, 0x0C060C02u) | 0x64006400u); kd[3] = as_h2(byte_perm(h0, l0, 0x0C070C03u) | 0x64006400u);
-            kd[4] = as_h2(byte_perm(h1, l1, 0x0C040C00u) | 0x64006400u); kd[5] = as_h2(byte_perm(h1, l1, 0x0C050C01u) | 0x64006400u);
-            kd[6] = as_h2(byte_perm(h1, l1, 0x0C060C02u) | 0x64006400u); kd[7] = as_h2(byte_perm(h1, l1, 0x0C070C03u) | 0x64006400u);
+            q_code_pairs<KBITS>(kcs[un], kd);
             const float ks = (float)kss[un] * (1.0f / 32.0f);
             const int kpos = base0 + un * STEP + group;
             #pragma unroll
@@ -322,13 +358,8 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
         #pragma unroll
         for (int un = 0; un < AQ_UNROLL; un++)
         {
-            const u32 l0 = vcs[un].x & 0x0F0F0F0Fu, h0 = (vcs[un].x >> 4) & 0x0F0F0F0Fu;
-            const u32 l1 = vcs[un].y & 0x0F0F0F0Fu, h1 = (vcs[un].y >> 4) & 0x0F0F0F0Fu;
             f16x2 vd[8];
-            vd[0] = as_h2(byte_perm(h0, l0, 0x0C040C00u) | 0x64006400u); vd[1] = as_h2(byte_perm(h0, l0, 0x0C050C01u) | 0x64006400u);
-            vd[2] = as_h2(byte_perm(h0, l0, 0x0C060C02u) | 0x64006400u); vd[3] = as_h2(byte_perm(h0, l0, 0x0C070C03u) | 0x64006400u);
-            vd[4] = as_h2(byte_perm(h1, l1, 0x0C040C00u) | 0x64006400u); vd[5] = as_h2(byte_perm(h1, l1, 0x0C050C01u) | 0x64006400u);
-            vd[6] = as_h2(byte_perm(h1, l1, 0x0C060C02u) | 0x64006400u); vd[7] = as_h2(byte_perm(h1, l1, 0x0C070C03u) | 0x64006400u);
+            q_code_pairs<VBITS>(vcs[un], vd);
             float vfl[16];
             #pragma unroll
             for (int i = 0; i < 8; i++) { vfl[2 * i] = (float)vd[i].x; vfl[2 * i + 1] = (float)vd[i].y; }
@@ -346,7 +377,7 @@ KERNEL void __launch_bounds__(AQ_WAVES * 64) attn_q4_decode_kernel(const AttnQ4A
     for (int r = 0; r < RB; r++)
     {
         #pragma unroll
-        for (int e = 0; e < 16; e++) o[r][e] -= 1032.0f * osub[r];
+        for (int e = 0; e < 16; e++) o[r][e] -= q_bias<VBITS>() * osub[r];
     }
 
     // ---- the step's own keys / values, still fp16 (the reference attends over them before they are quantised) -------------
@@ -544,7 +575,7 @@ KERNEL void __launch_bounds__(256) attn_q4_combine_kernel(const AttnQ4Args a, in
 
 static int ilog2_exact_q4(int x) { int s = 0; while ((1 << s) < x) s++; return (1 << s) == x ? s : -1; }
 
-template <int HDIM>
+template <int HDIM, int KBITS, int VBITS>
 static void launch_q4(const AttnQ4Args& a, int rb, dim3 grid, void* stream, bool fused = false)
 {
     static bool attr_done_fused[EXL2_MAX_DEVICES] = {false};
@@ -555,8 +586,8 @@ static void launch_q4(const AttnQ4Args& a, int rb, dim3 grid, void* stream, bool
     static bool attr_done[EXL2_MAX_DEVICES] = {false};
     if (exl2_first_on_device(attr_done))
     {
-        (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 4, false, KBITS, VBITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 2, false, KBITS, VBITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     if constexpr (HDIM == 128 || HDIM == 64)
     {
@@ -564,32 +595,41 @@ static void launch_q4(const AttnQ4Args& a, int rb, dim3 grid, void* stream, bool
         {
             if (exl2_first_on_device(attr_done_fused))
             {
-                (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 4, true, KBITS, VBITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                (void)hipFuncSetAttribute((const void*)attn_q4_decode_kernel<HDIM, 2, true, KBITS, VBITS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             }
             switch (rb)
             {
-                case 1: LAUNCH((attn_q4_decode_kernel<HDIM, 1, true>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
-                case 2: LAUNCH((attn_q4_decode_kernel<HDIM, 2, true>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
-                default: LAUNCH((attn_q4_decode_kernel<HDIM, 4, true>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
+                case 1: LAUNCH((attn_q4_decode_kernel<HDIM, 1, true, KBITS, VBITS>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
+                case 2: LAUNCH((attn_q4_decode_kernel<HDIM, 2, true, KBITS, VBITS>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
+                default: LAUNCH((attn_q4_decode_kernel<HDIM, 4, true, KBITS, VBITS>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
             }
             return;
         }
     }
     switch (rb)
     {
-        case 1: LAUNCH((attn_q4_decode_kernel<HDIM, 1>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
-        case 2: LAUNCH((attn_q4_decode_kernel<HDIM, 2>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
-        default: LAUNCH((attn_q4_decode_kernel<HDIM, 4>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
+        case 1: LAUNCH((attn_q4_decode_kernel<HDIM, 1, false, KBITS, VBITS>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
+        case 2: LAUNCH((attn_q4_decode_kernel<HDIM, 2, false, KBITS, VBITS>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
+        default: LAUNCH((attn_q4_decode_kernel<HDIM, 4, false, KBITS, VBITS>), grid, dim3(AQ_WAVES * 64), lds, stream, a); break;
     }
 }
 
-// Attention over a Q4 KV cache.  k_new / v_new == NULL: the cache holds all `total` keys.  Otherwise the last q_len keys
+template <int KBITS, int VBITS>
+static void launch_q(const AttnQ4Args& a, int head_dim, int rb, dim3 grid, void* stream, bool fused)
+{
+    if (head_dim == 64) launch_q4<64, KBITS, VBITS>(a, rb, grid, stream, fused);
+    else if (head_dim == 128) launch_q4<128, KBITS, VBITS>(a, rb, grid, stream, fused);
+    else launch_q4<256, KBITS, VBITS>(a, rb, grid, stream);
+}
+
+// Attention over a quantized KV cache (wbits 4 | 6 | 8: Q4, Q6 = 8-bit keys + 4-bit values, Q8).  k_new / v_new == NULL: the cache holds all `total` keys.  Otherwise the last q_len keys
 // (the step's own, k_new already rotated) are taken from these fp16 tensors -- the reference attends over the step's K/V
 // before quantising them (cache.py:517-556 runs after attention) -- and only keys < total - q_len come from the codes.
-// Same addressing / length conventions as exl2_paged_attn; codes [.., KVH, hd/2] uint8, scales [.., KVH, hd/32] fp16.
+// Same addressing / length conventions as exl2_paged_attn; codes [.., KVH, hd/2] uint8 on a 4-bit side, [.., KVH, hd] on an 8-bit
+// side, scales [.., KVH, hd/32] fp16.
 // Returns 1 without launching for shapes it does not cover (caller unpacks with exl2_q_to_fp16_kv + exl2_paged_attn).
-static int paged_attn_q4_impl(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+static int paged_attn_q4_impl(int wbits, const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
                        const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
                        int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
                        int page_size, int pages_per_seq, int len_const, int len_offset,
@@ -598,6 +638,7 @@ static int paged_attn_q4_impl(const void* q, const void* k_codes, const void* k_
                        const void* sin = nullptr, const void* cos = nullptr, int rope_style = -1, int sincos_size = 0)
 {
     const bool fused = rope_style >= 0;                     // the one-launch form: RoPE + pack of the step's rows inside this launch
+    EXL2_REQUIRE(wbits == 4 || wbits == 6 || wbits == 8, "paged_attn_q: wbits must be 4, 6 or 8 (got %d)", wbits);
     EXL2_REQUIRE(q && k_codes && k_scales && v_codes && v_scales && out, "paged_attn_q4: null argument");
     EXL2_REQUIRE(num_kv_heads > 0 && num_heads % num_kv_heads == 0, "paged_attn_q4: heads %d not a multiple of kv heads %d", num_heads, num_kv_heads);
     if (batch <= 0 || q_len <= 0) return EXL2_OK;
@@ -634,6 +675,9 @@ static int paged_attn_q4_impl(const void* q, const void* k_codes, const void* k_
     {
         const long long base = (long long)num_kv_heads * batch * rblocks;
         // 144 B per key: the stream is latency-bound, not bandwidth-bound -- many short splits (4 waves each)
+        // (measured at 4 bits only.  8-bit sides -- 208 / 272 B per key -- take the same policy and NOTHING has been measured for them yet:
+        // an A/B with tools/attn_bench.py --caches comes before any change here, DESIGN.md 3.1.  What does hold at every width: ~1024
+        // workgroups of 4 waves are 4 waves per SIMD, which is the occupancy the (8, x) instantiations have at one row per workgroup)
         nsplit = (int)((1024 + base - 1) / base);
         if (nsplit > 32) nsplit = 32;
         if (nsplit < 1) nsplit = 1;
@@ -651,9 +695,9 @@ static int paged_attn_q4_impl(const void* q, const void* k_codes, const void* k_
     // the length needed more than one split)
     if (nsplit > 1 && counters && (long long)n_counters >= (long long)batch * num_kv_heads * rblocks) a.counters = (u32*)counters;
     dim3 grid((unsigned)num_kv_heads, (unsigned)nsplit, (unsigned)(batch * rblocks));
-    if (head_dim == 64) launch_q4<64>(a, rb, grid, stream, fused);
-    else if (head_dim == 128) launch_q4<128>(a, rb, grid, stream, fused);
-    else launch_q4<256>(a, rb, grid, stream);
+    if (wbits == 4) launch_q<4, 4>(a, head_dim, rb, grid, stream, fused);
+    else if (wbits == 6) launch_q<8, 4>(a, head_dim, rb, grid, stream, fused);
+    else launch_q<8, 8>(a, head_dim, rb, grid, stream, fused);
     if (nsplit > 1 && !a.counters)
         LAUNCH(attn_q4_combine_kernel, dim3((unsigned)(batch * q_len * num_heads)), dim3(head_dim < 256 ? head_dim : 256), 0,
                stream, a, head_dim);
@@ -663,6 +707,19 @@ static int paged_attn_q4_impl(const void* q, const void* k_codes, const void* k_
 
 extern "C" {
 
+// wbits = 4 | 6 | 8 (anything else is an error): the code widths of the two sides, as exl2_fp16_to_q_kv takes them.
+int exl2_paged_attn_q(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                      const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
+                      int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                      int page_size, int pages_per_seq, int len_const, int len_offset,
+                      float softmax_scale, int causal, int nsplit, void* scratch, long long scratch_bytes,
+                      const void* out_invperm, int wbits, void* stream)
+{
+    return paged_attn_q4_impl(wbits, q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
+                              num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, len_const, len_offset, softmax_scale, causal,
+                              nsplit, scratch, scratch_bytes, out_invperm, nullptr, 0, stream);
+}
+
 int exl2_paged_attn_q4(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
                        const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
                        int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
@@ -670,14 +727,26 @@ int exl2_paged_attn_q4(const void* q, const void* k_codes, const void* k_scales,
                        float softmax_scale, int causal, int nsplit, void* scratch, long long scratch_bytes,
                        const void* out_invperm, void* stream)
 {
-    return paged_attn_q4_impl(q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
-                              num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, len_const, len_offset, softmax_scale, causal,
-                              nsplit, scratch, scratch_bytes, out_invperm, nullptr, 0, stream);
+    return exl2_paged_attn_q(q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
+                             num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, len_const, len_offset, softmax_scale, causal,
+                             nsplit, scratch, scratch_bytes, out_invperm, 4, stream);
 }
 
 // The same with `counters`: n_counters >= batch * q_len * num_heads (one per query row always suffices; fewer than the launch needs: the combine launch runs instead) u32 tickets, ZERO before the first
 // call (every launch leaves them zero): the split partials are merged by the last split to finish, inside the launch -- one launch
 // instead of two.  (exl2_attn_decode_fused's counters serve: same indexing, never used by both at once on a stream.)
+int exl2_paged_attn_q_merged(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                             const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
+                             int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                             int page_size, int pages_per_seq, int len_const, int len_offset,
+                             float softmax_scale, int causal, int nsplit, void* scratch, long long scratch_bytes,
+                             const void* out_invperm, void* counters, int n_counters, int wbits, void* stream)
+{
+    return paged_attn_q4_impl(wbits, q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
+                              num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, len_const, len_offset, softmax_scale, causal,
+                              nsplit, scratch, scratch_bytes, out_invperm, counters, n_counters, stream);
+}
+
 int exl2_paged_attn_q4_merged(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
                               const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
                               int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
@@ -685,17 +754,30 @@ int exl2_paged_attn_q4_merged(const void* q, const void* k_codes, const void* k_
                               float softmax_scale, int causal, int nsplit, void* scratch, long long scratch_bytes,
                               const void* out_invperm, void* counters, int n_counters, void* stream)
 {
-    return paged_attn_q4_impl(q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
-                              num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, len_const, len_offset, softmax_scale, causal,
-                              nsplit, scratch, scratch_bytes, out_invperm, counters, n_counters, stream);
+    return exl2_paged_attn_q_merged(q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
+                                    num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, len_const, len_offset, softmax_scale, causal,
+                                    nsplit, scratch, scratch_bytes, out_invperm, counters, n_counters, 4, stream);
 }
 
-// The whole decode step over a Q4 cache in ONE launch: RoPE on q and k_new (NOT modified in memory: rotated on the way into the
-// kernel), Q4 pack of the rotated k_new and of v_new into the codes / scales at positions past + j (past = cache_seqlens[b], or
-// past_const without cache_seqlens), attention over the codes for keys below `past` and over the step's own rows in fp16, split
-// merge by ticket == exl2_rope_kv_append + exl2_fp16_to_q_kv + exl2_paged_attn_q4 (+ its combine launch).  Returns 1 without
-// launching for shapes it does not cover (head_dim != 128, partial rotary, > 64 query rows per kv head): the caller takes
-// exl2_rope_quant_append_q4 + exl2_paged_attn_q4_merged.
+// The whole decode step over a quantized cache in ONE launch: RoPE on q and k_new (NOT modified in memory: rotated on the way into the
+// kernel), pack of the rotated k_new and of v_new into the codes / scales at positions past + j (past = cache_seqlens[b], or
+// past_const without cache_seqlens) at the widths of `wbits`, attention over the codes for keys below `past` and over the step's own
+// rows in fp16, split merge by ticket == exl2_rope_kv_append + exl2_fp16_to_q_kv + exl2_paged_attn_q (+ its combine launch).  Returns 1
+// without launching for shapes it does not cover (head_dim not 128 / 64 with an even number of kv heads, partial rotary, > 64 query
+// rows per kv head): the caller takes exl2_rope_quant_append_q + exl2_paged_attn_q_merged.
+int exl2_attn_q_decode_fused(const void* q, const void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes,
+                             void* v_scales, void* out, const void* sin, const void* cos, const int* cache_seqlens,
+                             const int* block_table, int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                             int page_size, int pages_per_seq, int past_const, float softmax_scale, int rope_style, int sincos_size,
+                             int nsplit, void* scratch, long long scratch_bytes, void* counters, int n_counters,
+                             const void* out_invperm, int wbits, void* stream)
+{
+    EXL2_REQUIRE(rope_style >= 0 && rope_style <= 2, "attn_q_decode_fused: rope_style %d", rope_style);
+    return paged_attn_q4_impl(wbits, q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
+                              num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, past_const, q_len, softmax_scale, 1,
+                              nsplit, scratch, scratch_bytes, out_invperm, counters, n_counters, stream, sin, cos, rope_style, sincos_size);
+}
+
 int exl2_attn_q4_decode_fused(const void* q, const void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes,
                               void* v_scales, void* out, const void* sin, const void* cos, const int* cache_seqlens,
                               const int* block_table, int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
@@ -703,10 +785,9 @@ int exl2_attn_q4_decode_fused(const void* q, const void* k_new, const void* v_ne
                               int nsplit, void* scratch, long long scratch_bytes, void* counters, int n_counters,
                               const void* out_invperm, void* stream)
 {
-    EXL2_REQUIRE(rope_style >= 0 && rope_style <= 2, "attn_q4_decode_fused: rope_style %d", rope_style);
-    return paged_attn_q4_impl(q, k_codes, k_scales, v_codes, v_scales, k_new, v_new, out, cache_seqlens, block_table, batch, q_len,
-                              num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, past_const, q_len, softmax_scale, 1,
-                              nsplit, scratch, scratch_bytes, out_invperm, counters, n_counters, stream, sin, cos, rope_style, sincos_size);
+    return exl2_attn_q_decode_fused(q, k_new, v_new, k_codes, k_scales, v_codes, v_scales, out, sin, cos, cache_seqlens, block_table,
+                                    batch, q_len, num_heads, num_kv_heads, head_dim, page_size, pages_per_seq, past_const, softmax_scale,
+                                    rope_style, sincos_size, nsplit, scratch, scratch_bytes, counters, n_counters, out_invperm, 4, stream);
 }
 
 }  // extern "C"

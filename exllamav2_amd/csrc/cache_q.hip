@@ -135,6 +135,7 @@ struct RopeQ4Args
     int page_size, page_shift, pages_per_seq;
 };
 
+template <int KBITS, int VBITS>       // code widths of the two sides: (4, 4) Q4, (8, 4) Q6, (8, 8) Q8
 KERNEL void __launch_bounds__(64) rope_quant_q4_kernel(const RopeQ4Args a)
 {
     constexpr int HDIM = 128;
@@ -160,7 +161,7 @@ KERNEL void __launch_bounds__(64) rope_quant_q4_kernel(const RopeQ4Args a)
     if (is_v)
     {
         const f16x2 w = ((const f16x2*)(a.v_new + (((size_t)b * a.s + j) * a.KVH + h) * HDIM))[t];
-        q_pack_lane<4>(t, w, a.v_codes, a.v_scales, cache_off);
+        q_pack_lane<VBITS>(t, w, a.v_codes, a.v_scales, cache_off);
         return;
     }
     f16* x = is_q ? a.q + (((size_t)b * a.s + j) * a.H + h) * HDIM : a.k_new + (((size_t)b * a.s + j) * a.KVH + h) * HDIM;
@@ -173,7 +174,7 @@ KERNEL void __launch_bounds__(64) rope_quant_q4_kernel(const RopeQ4Args a)
         w = rope_lane_pair128(w, t, sr, cr, a.neox != 0);
         ((f16x2*)x)[t] = w;
     }
-    if (!is_q) q_pack_lane<4>(t, w, a.k_codes, a.k_scales, cache_off);
+    if (!is_q) q_pack_lane<KBITS>(t, w, a.k_codes, a.k_scales, cache_off);
 }
 
 static int ilog2_exact_cq(int x) { int s = 0; while ((1 << s) < x) s++; return (1 << s) == x ? s : -1; }
@@ -260,18 +261,20 @@ int exl2_q_to_fp16_kv(const void* k_in, void* k_out, const void* k_scales, const
                        offset, width, page_size, cache_seqlens, block_table, pages_per_seq, wbits, stream);
 }
 
-// RoPE on q and k_new in place + Q4 pack of the rotated k_new and of v_new into the cache at positions past_len (+ past_lens[b]) + j
-// through the block table (exl2_rope_kv_append's conventions; block_table == NULL: row b of a [batch, page_size = max_seq_len] cache).
-// One launch for exl2_rope_kv_append + exl2_fp16_to_q_kv (paged, wbits 4) of a decode step.  Returns 1 without launching for shapes
-// it does not cover (head_dim != 128, partial rotary): the caller takes the two entry points it replaces.
-int exl2_rope_quant_append_q4(void* q, void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
-                              const void* sin, const void* cos, int batch, int q_len, int num_heads, int num_kv_heads,
-                              int head_dim, int past_len, const int* past_lens, const int* block_table,
-                              int page_size, int pages_per_seq, int rope_style, int sincos_size, void* stream)
+// RoPE on q and k_new in place + pack of the rotated k_new and of v_new into the cache (wbits 4 | 6 | 8) at positions past_len
+// (+ past_lens[b]) + j through the block table (exl2_rope_kv_append's conventions; block_table == NULL: row b of a [batch, page_size =
+// max_seq_len] cache).  One launch for exl2_rope_kv_append + exl2_fp16_to_q_kv (paged) of a decode step.  Returns 1 without launching
+// for shapes it does not cover (head_dim != 128, partial rotary): the caller takes the two entry points it replaces.
+int exl2_rope_quant_append_q(void* q, void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                             const void* sin, const void* cos, int batch, int q_len, int num_heads, int num_kv_heads,
+                             int head_dim, int past_len, const int* past_lens, const int* block_table,
+                             int page_size, int pages_per_seq, int rope_style, int sincos_size, int wbits, void* stream)
 {
-    EXL2_REQUIRE(q && k_new && v_new && k_codes && k_scales && v_codes && v_scales, "rope_quant_append_q4: null argument");
-    EXL2_REQUIRE(rope_style == 0 || (sin && cos), "rope_quant_append_q4: sin/cos tables missing");
-    EXL2_REQUIRE(past_len != -1 || past_lens, "rope_quant_append_q4: past_len == -1 needs past_lens");
+    int kb = 0, vb = 0;
+    EXL2_REQUIRE(wbits_pair(wbits, &kb, &vb) == 0, "rope_quant_append_q: wbits must be 4, 6 or 8 (got %d)", wbits);
+    EXL2_REQUIRE(q && k_new && v_new && k_codes && k_scales && v_codes && v_scales, "rope_quant_append_q: null argument");
+    EXL2_REQUIRE(rope_style == 0 || (sin && cos), "rope_quant_append_q: sin/cos tables missing");
+    EXL2_REQUIRE(past_len != -1 || past_lens, "rope_quant_append_q: past_len == -1 needs past_lens");
     if (batch <= 0 || q_len <= 0) return EXL2_OK;
     if (head_dim != 128 || (rope_style != 0 && sincos_size > 0 && sincos_size != head_dim)) return 1;
     RopeQ4Args a;
@@ -282,10 +285,22 @@ int exl2_rope_quant_append_q4(void* q, void* k_new, const void* v_new, void* k_c
     a.b = batch; a.s = q_len; a.H = num_heads; a.KVH = num_kv_heads;
     a.past_len = past_len; a.neox = rope_style == 2; a.rope = rope_style != 0;      // ROPE_STYLE_* q_attn.cuh:13-15
     a.page_size = page_size; a.pages_per_seq = pages_per_seq; a.page_shift = ilog2_exact_cq(page_size);
-    EXL2_REQUIRE(!block_table || a.page_shift >= 0, "rope_quant_append_q4: page_size must be a power of two");
-    LAUNCH(rope_quant_q4_kernel, dim3((unsigned)(num_heads + 2 * num_kv_heads), (unsigned)q_len, (unsigned)batch), dim3(64), 0, stream, a);
+    EXL2_REQUIRE(!block_table || a.page_shift >= 0, "rope_quant_append_q: page_size must be a power of two");
+    const dim3 grid((unsigned)(num_heads + 2 * num_kv_heads), (unsigned)q_len, (unsigned)batch);
+    if (kb == 4) LAUNCH((rope_quant_q4_kernel<4, 4>), grid, dim3(64), 0, stream, a);
+    else if (vb == 4) LAUNCH((rope_quant_q4_kernel<8, 4>), grid, dim3(64), 0, stream, a);
+    else LAUNCH((rope_quant_q4_kernel<8, 8>), grid, dim3(64), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return EXL2_OK;
+}
+
+int exl2_rope_quant_append_q4(void* q, void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                              const void* sin, const void* cos, int batch, int q_len, int num_heads, int num_kv_heads,
+                              int head_dim, int past_len, const int* past_lens, const int* block_table,
+                              int page_size, int pages_per_seq, int rope_style, int sincos_size, void* stream)
+{
+    return exl2_rope_quant_append_q(q, k_new, v_new, k_codes, k_scales, v_codes, v_scales, sin, cos, batch, q_len, num_heads, num_kv_heads,
+                                    head_dim, past_len, past_lens, block_table, page_size, pages_per_seq, rope_style, sincos_size, 4, stream);
 }
 
 }  // extern "C"

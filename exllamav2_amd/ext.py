@@ -456,6 +456,97 @@ class ExtC:
             page_size, pps, int(rope_style), int(sincos_size), self._stream(q)))
         return rc == 0
 
+    # the same three for every quantized cache width (wbits 4 | 6 | 8; include/exl2_hip.h: exl2_*_q): an 8-bit side holds hd code
+    # bytes per head row, a 4-bit side hd / 2 -- Q6 = 8-bit keys + 4-bit values
+
+    @staticmethod
+    def _q_sides(name: str, wbits: int, hd: int, kvh: int, k_codes, k_scales, v_codes, v_scales) -> None:
+        if wbits not in (4, 6, 8): raise RuntimeError(f"{name}: wbits must be 4, 6 or 8 (got {wbits})")
+        kb, vb = (8 if wbits >= 6 else 4), (8 if wbits == 8 else 4)
+        for side, codes, scales, bits in (("k", k_codes, k_scales, kb), ("v", v_codes, v_scales, vb)):
+            if codes.dim() != 4 or scales.dim() != 4 or codes.dtype != torch.uint8 or scales.dtype != torch.float16:
+                raise RuntimeError(f"{name}: {side} codes / scales must be 4-D uint8 / float16")
+            if codes.shape[2] != kvh or codes.shape[3] != hd * bits // 8:
+                raise RuntimeError(f"{name}: {side}_codes {tuple(codes.shape)}: expected [.., {kvh}, {hd * bits // 8}] at {bits} bits")
+            if tuple(scales.shape) != (*codes.shape[:2], kvh, hd // 32):
+                raise RuntimeError(f"{name}: {side}_scales {tuple(scales.shape)}: expected {(*codes.shape[:2], kvh, hd // 32)}")
+            if not (codes.is_contiguous() and scales.is_contiguous()):
+                raise RuntimeError(f"{name}: {side} codes / scales must be contiguous")
+        if tuple(k_codes.shape[:2]) != tuple(v_codes.shape[:2]):
+            raise RuntimeError(f"{name}: k and v sides differ in [pages | batch, page_size]")
+
+    def paged_attn_q(self, q, k_codes, k_scales, v_codes, v_scales, out, cache_seqlens, block_table, wbits: int, len_const: int = 0,
+                     len_offset: int = 0, softmax_scale: float | None = None, causal: bool = True, nsplit: int = 0,
+                     scratch=None, k_new=None, v_new=None, out_invperm: int | None = None, counters=None) -> bool:
+        """paged_attn_q4 at the code widths of `wbits`; False when the shape needs the unpack route."""
+        b, s, nh, hd = q.shape
+        kvh = k_codes.shape[2]
+        self._q_sides("paged_attn_q", wbits, hd, kvh, k_codes, k_scales, v_codes, v_scales)
+        if (k_new is None) != (v_new is None): raise RuntimeError("paged_attn_q: k_new and v_new go together")
+        if k_new is not None and (tuple(k_new.shape) != (b, s, kvh, hd) or tuple(v_new.shape) != (b, s, kvh, hd)):
+            raise RuntimeError("paged_attn_q: k_new / v_new must be [b, q_len, KVH, hd]")
+        if tuple(out.shape) != tuple(q.shape): raise RuntimeError("paged_attn_q: out must have q's shape")
+        page_size = k_codes.shape[1]
+        pps = 0 if _is_none(block_table) else block_table.shape[1]
+        scale = hd ** -0.5 if softmax_scale is None else softmax_scale
+        sb = 0 if scratch is None else scratch.numel() * scratch.element_size()
+        args = (self._ptr(q, torch.float16, "q"), self._ptr(k_codes, torch.uint8, "k_codes"),
+                self._ptr(k_scales, torch.float16, "k_scales"), self._ptr(v_codes, torch.uint8, "v_codes"),
+                self._ptr(v_scales, torch.float16, "v_scales"), self._ptr(k_new, torch.float16, "k_new"),
+                self._ptr(v_new, torch.float16, "v_new"), self._ptr(out, torch.float16, "out"),
+                self._ptr(cache_seqlens, torch.int32, "cache_seqlens"), self._ptr(block_table, torch.int32, "block_table"),
+                b, s, nh, kvh, hd, page_size, pps, int(len_const), int(len_offset), float(scale), int(causal), int(nsplit),
+                self._ptr(scratch), sb, out_invperm or None)
+        if counters is not None:
+            rc = self.lib.check(self.lib.exl2_paged_attn_q_merged(*args, self._ptr(counters, torch.int32, "counters"), counters.numel(),
+                                                                  int(wbits), self._stream(q)))
+        else:
+            rc = self.lib.check(self.lib.exl2_paged_attn_q(*args, int(wbits), self._stream(q)))
+        return rc == 0
+
+    def attn_q_decode_fused(self, q, k_new, v_new, k_codes, k_scales, v_codes, v_scales, out, sin, cos, cache_seqlens, block_table,
+                            past_const: int, rope_style: int, scratch, counters, wbits: int, softmax_scale: float | None = None,
+                            nsplit: int = 0, out_invperm: int | None = None, sincos_size: int = 0) -> bool:
+        """attn_q4_decode_fused at the code widths of `wbits`.  False: shape not covered."""
+        b, s, nh, hd = q.shape
+        kvh = k_new.shape[2]
+        self._q_sides("attn_q_decode_fused", wbits, hd, kvh, k_codes, k_scales, v_codes, v_scales)
+        if tuple(k_new.shape) != (b, s, kvh, hd) or tuple(v_new.shape) != (b, s, kvh, hd):
+            raise RuntimeError("attn_q_decode_fused: k_new / v_new must be [b, q_len, KVH, hd]")
+        if tuple(out.shape) != tuple(q.shape): raise RuntimeError("attn_q_decode_fused: out must have q's shape")
+        page_size = k_codes.shape[1]
+        pps = 0 if _is_none(block_table) else block_table.shape[1]
+        scale = hd ** -0.5 if softmax_scale is None else softmax_scale
+        sb = 0 if scratch is None else scratch.numel() * scratch.element_size()
+        rc = self.lib.check(self.lib.exl2_attn_q_decode_fused(
+            self._ptr(q, torch.float16, "q"), self._ptr(k_new, torch.float16, "k_new"), self._ptr(v_new, torch.float16, "v_new"),
+            self._ptr(k_codes, torch.uint8, "k_codes"), self._ptr(k_scales, torch.float16, "k_scales"),
+            self._ptr(v_codes, torch.uint8, "v_codes"), self._ptr(v_scales, torch.float16, "v_scales"),
+            self._ptr(out, torch.float16, "out"), self._ptr(sin), self._ptr(cos),
+            self._ptr(cache_seqlens, torch.int32, "cache_seqlens"), self._ptr(block_table, torch.int32, "block_table"),
+            b, s, nh, kvh, hd, page_size, pps, int(past_const), float(scale), int(rope_style), int(sincos_size), int(nsplit),
+            self._ptr(scratch), sb, self._ptr(counters, torch.int32, "counters"), counters.numel(), out_invperm or None,
+            int(wbits), self._stream(q)))
+        return rc == 0
+
+    def rope_quant_append_q(self, q, k_new, v_new, k_codes, k_scales, v_codes, v_scales, sin, cos, past_len: int, past_lens,
+                            block_table, rope_style: int, wbits: int, sincos_size: int = 0) -> bool:
+        """rope_quant_append_q4 at the code widths of `wbits`.  False: shape not covered."""
+        b, s, nh, hd = q.shape
+        kvh = k_new.shape[2]
+        self._q_sides("rope_quant_append_q", wbits, hd, kvh, k_codes, k_scales, v_codes, v_scales)
+        if tuple(k_new.shape) != (b, s, kvh, hd) or tuple(v_new.shape) != (b, s, kvh, hd):
+            raise RuntimeError("rope_quant_append_q: k_new / v_new must be [b, q_len, KVH, hd]")
+        page_size = k_codes.shape[1]
+        pps = 0 if _is_none(block_table) else block_table.shape[1]
+        rc = self.lib.check(self.lib.exl2_rope_quant_append_q(
+            self._ptr(q, torch.float16, "q"), self._ptr(k_new, torch.float16, "k_new"), self._ptr(v_new, torch.float16, "v_new"),
+            self._ptr(k_codes, torch.uint8, "k_codes"), self._ptr(k_scales, torch.float16, "k_scales"),
+            self._ptr(v_codes, torch.uint8, "v_codes"), self._ptr(v_scales, torch.float16, "v_scales"),
+            self._ptr(sin), self._ptr(cos), b, s, nh, kvh, hd, int(past_len), self._ptr(past_lens), self._ptr(block_table),
+            page_size, pps, int(rope_style), int(sincos_size), int(wbits), self._stream(q)))
+        return rc == 0
+
     def rope_kv_append(self, q, k_new, v_new, k_cache, v_cache, sin, cos, past_len: int, past_lens, block_table,
                        rope_style: int, sincos_size: int = 0) -> None:
         b, s, nh, hd = q.shape

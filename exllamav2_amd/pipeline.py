@@ -25,7 +25,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from .cache import ExLlamaV2Cache, ExLlamaV2Cache_Q4, PAGE_SIZE
+from .cache import ExLlamaV2Cache, ExLlamaV2Cache_Q4, PAGE_SIZE, cache_class  # noqa: F401
 from .comm import ring_exchange
 from .model import ExLlamaV2
 from .synth import synth_checkpoint
@@ -51,7 +51,7 @@ class PipelineStage:
                               with_head=self.last)
         self.model = ExLlamaV2(cfg, device=device, ext=ext).load(ck, layers=layers)
         self.ext = self.model.ext
-        cache_cls = ExLlamaV2Cache_Q4 if cache_type == "q4" else ExLlamaV2Cache
+        cache_cls = cache_class(cache_type)                      # fp16 | q4 | q6 | q8
         self.cache = cache_cls(self.model, batch_size=n_seqs, max_seq_len=max_seq_len)
         pages = max_seq_len // PAGE_SIZE
         dev = self.device

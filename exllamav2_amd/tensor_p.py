@@ -420,7 +420,7 @@ def run_tp_bench(cfg, args, rank: int, world: int, device, ext=None):
     collectives, so it is not captured into a HIP graph here."""
     import time
 
-    from .cache import ExLlamaV2Cache, ExLlamaV2Cache_Q4
+    from .cache import cache_class
     from .synth import synth_checkpoint
     max_seq = max(2048, ((args.ctx + args.steps + args.warmup + 1 + 255) // 256) * 256)
     cfg = dataclasses.replace(cfg, max_seq_len=max_seq)
@@ -436,7 +436,7 @@ def run_tp_bench(cfg, args, rank: int, world: int, device, ext=None):
         del ck
     sync()
     t_load = time.perf_counter() - t_load
-    cache_cls = ExLlamaV2Cache_Q4 if getattr(args, "cache", "fp16") == "q4" else ExLlamaV2Cache
+    cache_cls = cache_class(getattr(args, "cache", "fp16"))     # fp16 | q4 | q6 | q8
     cache = cache_cls(model, batch_size=args.batch, max_seq_len=max_seq)
     dec = TPGreedyDecoder(model, cache, batch_size=args.batch)
     dec.reset(torch.tensor([1] * args.batch), args.ctx)

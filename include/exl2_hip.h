@@ -225,6 +225,33 @@ int exl2_rope_quant_append_q4(void* q, void* k_new, const void* v_new, void* k_c
                               int head_dim, int past_len, const int* past_lens, const int* block_table,
                               int page_size, int pages_per_seq, int rope_style, int sincos_size, void* stream);
 
+/* The four entries above for every quantized cache width: wbits = 4 (Q4), 6 (Q6: 8-bit keys, 4-bit values; cache.cu:259-276) or
+   8 (Q8), as exl2_fp16_to_q_kv takes it; any other value is an error.  An 8-bit side holds one byte per element in element order
+   (codes [.., KVH, hd] u8), a 4-bit side two elements per byte ([.., KVH, hd / 2]); scales [.., KVH, hd / 32] fp16 on both.  Same
+   kernels, same conventions and return values; the *_q4 entries are these with wbits = 4. */
+int exl2_paged_attn_q(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                      const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
+                      int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                      int page_size, int pages_per_seq, int len_const, int len_offset,
+                      float softmax_scale, int causal, int nsplit, void* scratch, long long scratch_bytes,
+                      const void* out_invperm, int wbits, void* stream);
+int exl2_paged_attn_q_merged(const void* q, const void* k_codes, const void* k_scales, const void* v_codes, const void* v_scales,
+                             const void* k_new, const void* v_new, void* out, const int* cache_seqlens, const int* block_table,
+                             int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                             int page_size, int pages_per_seq, int len_const, int len_offset,
+                             float softmax_scale, int causal, int nsplit, void* scratch, long long scratch_bytes,
+                             const void* out_invperm, void* counters, int n_counters, int wbits, void* stream);
+int exl2_attn_q_decode_fused(const void* q, const void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes,
+                             void* v_scales, void* out, const void* sin, const void* cos, const int* cache_seqlens,
+                             const int* block_table, int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                             int page_size, int pages_per_seq, int past_const, float softmax_scale, int rope_style, int sincos_size,
+                             int nsplit, void* scratch, long long scratch_bytes, void* counters, int n_counters,
+                             const void* out_invperm, int wbits, void* stream);
+int exl2_rope_quant_append_q(void* q, void* k_new, const void* v_new, void* k_codes, void* k_scales, void* v_codes, void* v_scales,
+                             const void* sin, const void* cos, int batch, int q_len, int num_heads, int num_kv_heads,
+                             int head_dim, int past_len, const int* past_lens, const int* block_table,
+                             int page_size, int pages_per_seq, int rope_style, int sincos_size, int wbits, void* stream);
+
 /* ---- fused modules --------------------------------------------------------------------------------------------------- */
 
 /* make_q_attn (ext_qattn.cpp:24-104), q_attn_forward_1 (:115-159), q_attn_forward_2 (:161-191) */
