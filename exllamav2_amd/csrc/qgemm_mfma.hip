@@ -26,14 +26,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-#ifndef MF_KILL
-#define MF_KILL 0                        // timing experiments (results WRONG): 1 no X copies, 2 no weight decode, 4 no multiply
-#endif
-#ifdef MF_NOFENCE
-#define MF_FENCE() do { } while (0)
-#else
-#define MF_FENCE() sched_fence()
-#endif
 #define MF_BN 256
 #ifndef MF_WPRE_MIN_ROWS
 #define MF_WPRE_MIN_ROWS 129             // rows from which the weights are decoded once per call (wfrag_kernel): every call this file
@@ -82,7 +74,6 @@ DEV void load_raw(TileRaw& R, const QMatDev& m, const u32* sc_ptr, u32 tile_stri
 template <int BITS, bool GPTQ, int H>
 DEV void decode_half(const TileRaw& R, u8* w_stage, int wv, int lane)
 {
-    if (MF_KILL & 2) { if (lane == 99) *(u32*)(w_stage + wv * 64) = R.w[0][0] ^ R.w[1][0]; return; }
     #pragma unroll
     for (int t = 0; t < 2; t++)
     {
@@ -109,7 +100,7 @@ DEV void decode_half(const TileRaw& R, u8* w_stage, int wv, int lane)
             const f16x8 b = {b0.x, b0.y, b1.x, b1.y, b2.x, b2.y, b3.x, b3.y};
             *(f16x8*)(w_stage + ((size_t)(((2 * wv + t) * 2 + qq) * 64 + lane)) * 16) = b;
         }
-        MF_FENCE();             // one tile's decode temporaries at a time (register budget: the accumulators stay live)
+        sched_fence();             // one tile's decode temporaries at a time (register budget: the accumulators stay live)
     }
 }
 
@@ -149,7 +140,6 @@ template <int MT, bool PIPE = false>
 DEV void multiply_stage(const u8* x_stage, const u8* w_stage, int nv, int wm, int wn, int lane, f32x4 (&acc)[MT][4])
 {
     const int i16 = lane & 15, j4 = lane >> 4, sw = (lane >> 1) & 7;
-    if (MF_KILL & 4) return;
     if constexpr (!PIPE)
     {
         // (the kernels that decode inside the K loop have no registers to spare: fragments of one chunk at a time)
@@ -171,7 +161,7 @@ DEV void multiply_stage(const u8* x_stage, const u8* w_stage, int nv, int wm, in
                     for (int nt = 0; nt < 4; nt++) acc[mt][nt] = mfma_16x16x32_f16(wf[nt], xf, acc[mt][nt]);
                 }
             }
-            MF_FENCE();
+            sched_fence();
         }
         return;
     }
@@ -200,10 +190,10 @@ DEV void multiply_stage(const u8* x_stage, const u8* w_stage, int nv, int wm, in
                 if (mt + 1 < MT) xf[(mt + 1) & 1] = x_frag(kq, mt + 1);
                 else if (next_chunk) xf[(mt + 1) & 1] = x_frag(1, 0);
                 if (kq == 0 && mt < 4 && next_chunk) wf[1][mt] = w_frag(1, mt);
-                MF_FENCE();
+                sched_fence();
                 #pragma unroll
                 for (int nt = 0; nt < 4; nt++) acc[mt][nt] = mfma_16x16x32_f16(wf[kq][nt], xf[mt & 1], acc[mt][nt]);
-                MF_FENCE();
+                sched_fence();
             }
         }
     }
@@ -228,7 +218,6 @@ template <int MT>
 DEV void issue_x(const MfCtx& x, int k0, int nv, u8* stage)
 {
     constexpr int PIECES = MT / 2;
-    if (MF_KILL & 1) return;
     #pragma unroll
     for (int i = 0; i < PIECES; i++)
     {

@@ -1,10 +1,10 @@
-// qgemv_lean.hip -- decode q_gemm for a CHAIN of modules, round 3: the launch shape the MI355X measurements asked for.
+// qgemv_lean.hip -- decode q_gemm for a CHAIN of modules: the launch shape the MI355X measurements asked for.
 //
 // Replaces gemm_half_q_half_kernel (exllamav2_ext/cuda/q_gemm_kernel.cuh:140-565) + rms_norm_kernel (rms_norm.cu:33-175)
 // + act_mul_kernel (q_mlp_activation.cuh:54-112) on the decode path, as composed by QAttn::forward_cuda_1 / _2
 // (q_attn.cu:153-345) and QMLP::forward_run_ (q_mlp.cu:153-236).  Same host interface as qgemv_flat.hip (FlatIn); that
-// kernel remains the route for what this one declines (> LEAN_MAX_M rows, grouped MoE launches, shares too big for the
-// register stream).
+// kernel remains the route for what this one declines (> LEAN_MAX_ROWS rows, shares no geometry below can split, plans without
+// an instantiation in LEAN_DENSE_KERNELS).
 //
 // Why another shape (profiles/r02_trace_flat.txt, profiles/history/r03_lean_probe.txt, profiles/history/r03_trace_lean_v2.txt): the round-2
 // kernel is ONE 1024-thread workgroup per CU whose 16 waves share a scalar unit, plan their split on the device
@@ -18,13 +18,19 @@
 //     tile, tiles per workgroup, pairing) is a template parameter and the matrix is blockIdx.y, so the addresses of the
 //     header, the matrix block and the wave record depend on nothing but built-in ids: ONE batch of scalar loads, then
 //     the first weight request;
-//   * every wave requests its WHOLE share at entry into registers (<= LeanDepth items, no ring, no loop: what does not
-//     fit is declined);
+//   * every wave requests its share at entry into registers: <= lean_depth() items in one go, the last ones of them behind the
+//     staging copies and decoded as they land (the pipelined form).  A longer share takes several register loads where the host
+//     plans them: items of <= LEAN_S8_PASS_BITS bits as a ring (item q of the next load is requested when item q of this one
+//     is decoded), wider items one whole load after the other.  What no geometry holds that way is declined;
 //   * the prologue is wave-private: a wave copies only ITS K slice of the activations (LDS-DMA; RMSNorm applied in
 //     registers on the way when the producer left the residual stream un-normalised) and ITS rows of the scale table
 //     into its own LDS area -- no workgroup barrier before the decode;
 //   * partial sums of a tile meet in LDS (one barrier, fixed order = deterministic); cross-workgroup combines through
 //     memory were measured and lose 2-10 us (r03_lean_probe.txt, c1 rows).
+// Later forms for what the wave-private slices do not cover are described at lean_body: ROWS / WALK (5-16 rows staged once per
+// workgroup), XMEM (activations read from memory item by item), LOADS (one row of a long K), DEP (overlapped chain), MOE
+// (grouped experts).  The host side: lean_plan_matrix splits a tile over the waves, qgemv_lean_launch tries the candidate
+// geometries of a form in order, and the plan's key selects the one kernel of LEAN_DENSE_KERNELS / LEAN_MOE_KERNELS that runs it.
 #include "qgemv_common.h"
 #include "qgemv_flat.h"
 #include "qgemv_lean.h"
@@ -37,66 +43,25 @@
 #include <vector>
 #include <mutex>
 
-// tuning switches (A/B builds through tools/build_variant.sh; the defaults are what the MI355X runs picked)
-#ifndef LEAN_PRESCALE
-#define LEAN_PRESCALE 1               // 1: general items scale the weights (fp16, reconstruct()'s rounding); 0: four scales on four partial sums
-#endif
-#ifndef LEAN_KILL
-#define LEAN_KILL 0                   // instruction-count / timing experiments (results are WRONG): 1 no decode (the loads vanish too), 4 no epilogue, 8 loads kept, decode = xor
-#endif
-#ifndef LEAN_REPEAT
-#define LEAN_REPEAT 0                 // timing experiment (results are WRONG): > 0 = the decode of a wave's share runs that many times
-#endif
-#ifndef LEAN_LOWBITS
-#define LEAN_LOWBITS 1                // 0: no 2 / 3-bit register stream (code-size experiment; such segments would be wrong)
-#endif
-#ifndef LEAN_RAW2
-#define LEAN_RAW2 1                   // 4-bit items: the matrix cores get the UN-subtracted codes (half2 1024 + q / 64 + q: one v_and_or_b32 per pair, no
-#endif                                // v_pk_add / v_pk_fma) and the constant part leaves through a second MFMA per chunk against a constant B fragment
-                                      // -(1024 + z) / -(64 + z): 20 vector instructions per item instead of 50, no pre-pass (round 6; A/B in profiles/r06_raw2_ab.txt)
-#ifndef LEAN_DUO
-#define LEAN_DUO 0                    // 2 / 3-bit items whose groups are chunk pairs (group size 64): one scale per pair on the pair's fp32 sum (lean_item_general).
-                                      // Built and measured in round 6 (profiles/r09e_ab_*_duo.txt, same box): 16 packed multiplies + 2 scale reads fewer per
-                                      // item move the 70B gate|up launch 48.5 -> 48.2 us (the launch is NOT bound by instruction issue), Mixtral bs=1 +0.8 %,
-                                      // and the larger code costs the LOADS instantiation 6 spilled registers (70B down 33.8 -> 36.5 us, 70B -1.7 %): off
-#endif
-#ifndef LEAN_ITEM_FENCE
-#define LEAN_ITEM_FENCE 1             // a scheduling fence behind every item's decode (register pressure); 0: the compiler may interleave items (A/B experiment)
-#endif
-#ifndef LEAN_BUF_DMA
-#define LEAN_BUF_DMA 1                // the wave-private staging copies in the buffer form (hw.h: dma_buf_to_lds16): counted waits stay exact
-#endif
-#if LEAN_BUF_DMA
+// the wave-private staging copies, in the buffer form (hw.h: dma_buf_to_lds16): counted waits stay exact
 #define LEAN_DMA(base, off_bytes, lds) dma_buf_to_lds16(base, (u32)(off_bytes), lds)
 #define LEAN_DMA_X(base, off_bytes, lds) dma_buf_to_lds16_agent(base, (u32)(off_bytes), lds)     // activations: another launch wrote them
-#else
-#define LEAN_DMA_X(base, off_bytes, lds) dma_to_lds16((const u8*)(base) + (size_t)(off_bytes), lds)
-#define LEAN_DMA(base, off_bytes, lds) dma_to_lds16((const u8*)(base) + (size_t)(off_bytes), lds)
-#endif
 #define LEAN_MARK(id) ASM_MARK(id)     // (hw.h: a numbered comment in the gfx950 code; the emulation twin's hw_emu.h makes it nothing)
-#ifndef LEAN_XMEM_AHEAD
 #define LEAN_XMEM_AHEAD 3             // XMEM form: items whose A operands are in registers or in flight (16 registers each)
-#endif
 #define LEAN_X_PIECES_BASE 4           // 1 KB copy instructions per activation row of a wave's slice (stage_copies; lean_plan_matrix declines longer slices)
 #define LEAN_X_PIECES_PAIR_LOADS 6     // ... of the pair geometry with several register loads per wave (its own instantiation)
 #define LEAN_MAX_WAVES 16
 #define LEAN_RECORDS 48               // wave records in the argument block: matrices x waves per tile (q|k|v at 16 waves)
 #define LEAN_MAX_PASSES 4             // 16-wave geometry: a wave's share may be this many register loads (qgemv_lean_kernel, further passes)
-#ifndef LEAN_S8_PASSES
 #define LEAN_S8_PASSES 2              // 8-wave geometry, launches of several matrices (q|k|v): register loads a share may take (1 = round-4 behaviour)
-#endif
-#ifndef LEAN_S8_PASS_BITS
 #define LEAN_S8_PASS_BITS 4           // ... for items of at most this many bits; also the widest items decoded as a RING in either geometry (wider decoders + a full
-                                      // ring of requests do not fit 80 registers: spills, and the 5-bit pipelined region of the 16-wave kernel lost its counted wait)
-#endif
-#ifndef LEAN_PASS_RING
-#define LEAN_PASS_RING 1              // shares of several register loads: item q of the NEXT load is requested as soon as item q of this one is decoded
-#endif
+                                      // ring of requests do not fit 80 registers: spills, and the 5-bit pipelined region of the 16-wave kernel lost its counted wait).
+                                      // In a ring, item q of the NEXT load is requested as soon as item q of this one is decoded
 #define LEAN_MAX_PART 512             // partial sums of squares per row a chain-out launch may publish (hidden 8192 = 512 tiles; the
                                       // host's ss buffers are [rows, 512]; the round-2 kernel reads at most 256 and declines more)
 #define LEAN_LDS_BUDGET (40u * 1024u)  // per 8 waves: four 8-wave / two 16-wave workgroups stay resident on a CU
 
-// What one wave of a workgroup does for its tile: ONE run of full items of one bit width (requested into registers, <= LeanDepth
+// What one wave of a workgroup does for its tile: ONE run of full items of one bit width (requested into registers, <= lean_depth()
 // of them) plus, when the run ends in a partial super-chunk and this wave holds its end, that partial item (it lives in the
 // matrix' side buffer); one contiguous range of the activation row, one contiguous range of scale-table rows, its private LDS
 // area.  64 bytes = one scalar load.
@@ -158,26 +123,15 @@ struct LeanArgs
 
 // items of one bit width a wave may hold in registers (<= 25 dwords per lane in flight)
 // (S = 4: the 8-wave gate|up workgroup, built for 6 waves per SIMD = 80 registers -- a wave there holds 8 items of <= 4 bits)
-template <int BITS, int S> struct LeanDepth
-{
-    static constexpr int v = S == 4 ? (BITS == 8 ? 4 : BITS == 6 ? 5 : BITS == 5 ? 6 : BITS == 2 ? 10 : 8)
-                                    : (BITS == 8 ? 3 : BITS == 6 ? 4 : BITS == 5 ? 5 : BITS == 4 ? 6 : BITS == 2 ? 10 : 8);
-};
-// how many of those (the LAST ones of a share) are requested behind the fence load and decoded one by one as they land
-// (qgemv_lean_kernel: head); 0 = the round-3 form only.  LEAN_PIPE: 0 off, 1 = D / 2, 2 = D - 2 (at least 1)
-#ifndef LEAN_PIPE
-#define LEAN_PIPE 2
-#endif
-template <int BITS, int S> struct LeanTail
-{
-    static constexpr int D = LeanDepth<BITS, S>::v;
-    static constexpr int v = LEAN_PIPE == 0 ? 0 : LEAN_PIPE == 1 ? D / 2 : (D - 2 > 1 ? D - 2 : 1);
-};
-static int lean_depth(int bits, int S)
+// (one table for the kernel's register arrays and the host's split)
+constexpr int lean_depth(int bits, int S)
 {
     return S == 4 ? (bits == 8 ? 4 : bits == 6 ? 5 : bits == 5 ? 6 : bits == 2 ? 10 : 8)
                   : (bits == 8 ? 3 : bits == 6 ? 4 : bits == 5 ? 5 : bits == 4 ? 6 : bits == 2 ? 10 : 8);
 }
+// how many of those (the LAST ones of a share) are requested behind the fence load and decoded one by one as they land
+// (qgemv_lean_kernel: head): all but two, at least one
+constexpr int lean_tail(int bits, int S) { return lean_depth(bits, S) - 2 > 1 ? lean_depth(bits, S) - 2 : 1; }
 
 struct LeanCtx
 {
@@ -191,7 +145,6 @@ struct LeanCtx
 // MFMAs against the staged activations -> the group scale on the fp32 partial sum.  Same arithmetic as gemv_super
 // (qgemv_common.h).
 // PRE (the XMEM form of the kernel): the four A operands were requested from MEMORY ahead of time and arrive in `pre`.
-#if LEAN_RAW2
 // B fragment of one 32-row chunk straight from its packed dword: pairs (e = 0, 1) and (e = 4, 5) as 1024 + q, (2, 3) and (6, 7) as 64 + q
 // (the nibble sits where the half's unit bit is: 0x6400 = 1024, ulp 1; 0x5400 = 64, ulp 1 / 16).  Plain C so that the compiler sees
 // the VALU write in front of the MFMA (an inline-asm and_or feeding an MFMA hides the hazard: profiles/history/r05_raw4_experiment.txt).
@@ -214,7 +167,6 @@ DEV Raw4K raw4_consts()
     pin_scalar(k.m_lo); pin_scalar(k.m_hi); pin_vector(k.k_lo); pin_vector(k.k_hi);
     return k;
 }
-#endif
 
 template <int BITS, bool GPTQ, bool PRE = false>
 DEV void lean_item_uniform(const LaneWords<BITS>& lw, const LeanCtx& cx, int chunk, int g, int lane, f32x4& acc, const f16x8* pre = nullptr)
@@ -223,7 +175,6 @@ DEV void lean_item_uniform(const LaneWords<BITS>& lw, const LeanCtx& cx, int chu
     const int mrow = c < cx.M ? c : cx.M - 1;
     const f16* arow = cx.x_lds + mrow * cx.x_stride + (chunk - cx.xc0) * 32 + 8 * j;
     const float s = (float)cx.sc_lds[g * 16 + c];
-#if LEAN_RAW2
     if constexpr (BITS == 4)
     {
         const Raw4K k = raw4_consts();
@@ -244,7 +195,6 @@ DEV void lean_item_uniform(const LaneWords<BITS>& lw, const LeanCtx& cx, int chu
         for (int i = 0; i < 4; i++) acc[i] = fmaf(s, part[i], acc[i]);
         return;
     }
-#endif
     ZC zc[4];
     if constexpr (GPTQ) zc[0] = make_zc(cx.zp_lds[g * 16 + c]);
     else zc[0] = make_zc((f16)(float)(1 << (BITS - 1)));
@@ -269,7 +219,6 @@ DEV void lean_item_uniform(const LaneWords<BITS>& lw, const LeanCtx& cx, int chu
 // matrix' chunk -> group map).  The scale goes onto the WEIGHTS here -- fp16 (code - zero) * fp16 scale, one rounding: exactly
 // reconstruct()'s value (q_matrix.cu:328-553) -- so the four chunks still accumulate into one fp32 chain and the item
 // needs no more registers than the uniform form (four scales on the partial sums cost 13 more, i.e. a workgroup per CU).
-#if LEAN_PRESCALE
 template <int BITS, bool GPTQ, bool PRE = false>
 DEV void lean_item_general(const LaneWords<BITS>& lw, const LeanCtx& cx, int chunk, int cs, int g0, int gshift, int gphase, int nvalid,
                            int lane, f32x4& acc, const f16x8* pre = nullptr)
@@ -277,7 +226,6 @@ DEV void lean_item_general(const LaneWords<BITS>& lw, const LeanCtx& cx, int chu
     const int c = lane & 15, j = lane >> 4;
     const int mrow = c < cx.M ? c : cx.M - 1;
     const f16* arow = cx.x_lds + mrow * cx.x_stride + (chunk - cx.xc0) * 32 + 8 * j;
-#if LEAN_RAW2
     if constexpr (BITS == 4)
     {
         // a scale per chunk: each chunk's two MFMAs start from zero and the scale goes onto the fp32 sums (the same value
@@ -304,43 +252,6 @@ DEV void lean_item_general(const LaneWords<BITS>& lw, const LeanCtx& cx, int chu
         }
         return;
     }
-#endif
-#if LEAN_DUO
-    if constexpr (BITS <= 3 && !GPTQ)
-    {
-        // round 6: groups of 64 rows on chunk-pair boundaries (2 / 3-bit items of the 2.5 / 3.5 bpw recipes: q, k, o, gate, up of the 70B) --
-        // the two chunks of a group accumulate into one fp32 chain and the group's scale goes onto that sum, as the uniform form does
-        // for a whole item (for a one-hot row still reconstruct()'s value: fp16 scale x small integer is exact in fp32): 8 fp32
-        // multiply-adds and two scale reads per item instead of 16 packed multiplies and four reads.  At these widths the launch is bound
-        // by instruction issue (70B gate|up: ~520 cycles per item and SIMD).
-        if (gshift == 1 && (gphase & 1) == 0 && nvalid == 4)                  // (cs is a multiple of 4; uniform over the wave)
-        {
-            const ZC z = make_zc((f16)(float)(1 << (BITS - 1)));
-            ZC zc4[4] = {z, z, z, z};
-            f16x2 p[16];
-            dequant_super<BITS>(lw.w, zc4, p);
-            const int gi = (g0 + ((cs + gphase) >> 1)) * 16 + c;
-            const float s01 = (float)cx.sc_lds[gi], s23 = (float)cx.sc_lds[gi + 16];
-            #pragma unroll
-            for (int h = 0; h < 2; h++)
-            {
-                f32x4 part = {0.0f, 0.0f, 0.0f, 0.0f};
-                #pragma unroll
-                for (int q = 2 * h; q < 2 * h + 2; q++)
-                {
-                    const f16x8 b = {p[4 * q].x, p[4 * q].y, p[4 * q + 1].x, p[4 * q + 1].y, p[4 * q + 2].x, p[4 * q + 2].y, p[4 * q + 3].x, p[4 * q + 3].y};
-                    f16x8 a;
-                    if constexpr (PRE) a = pre[q]; else a = *(const f16x8*)(arow + q * 32);
-                    part = mfma_16x16x32_f16(a, b, part);
-                }
-                const float sh = h ? s23 : s01;
-                #pragma unroll
-                for (int i = 0; i < 4; i++) acc[i] = fmaf(sh, part[i], acc[i]);
-            }
-            return;
-        }
-    }
-#endif
     ZC zc[4];
     if constexpr (GPTQ)
     {
@@ -372,47 +283,6 @@ DEV void lean_item_general(const LaneWords<BITS>& lw, const LeanCtx& cx, int chu
     #pragma unroll
     for (int i = 0; i < 4; i++) acc[i] += part[i];
 }
-#else
-template <int BITS, bool GPTQ, bool PRE = false>
-DEV void lean_item_general(const LaneWords<BITS>& lw, const LeanCtx& cx, int chunk, int cs, int g0, int gshift, int gphase, int nvalid,
-                           int lane, f32x4& acc, const f16x8* pre = nullptr)
-{
-    const int c = lane & 15, j = lane >> 4;
-    const int mrow = c < cx.M ? c : cx.M - 1;
-    const f16* arow = cx.x_lds + mrow * cx.x_stride + (chunk - cx.xc0) * 32 + 8 * j;
-    const f32x4 zero4 = {0.0f, 0.0f, 0.0f, 0.0f};
-    float s[4];
-    ZC zc[4];
-    #pragma unroll
-    for (int q = 0; q < 4; q++)
-    {
-        const int g = g0 + ((cs + (q < nvalid ? q : 0) + gphase) >> gshift);
-        s[q] = (float)cx.sc_lds[g * 16 + c];
-        if constexpr (GPTQ) zc[q] = make_zc(cx.zp_lds[g * 16 + c]);
-    }
-    if constexpr (!GPTQ)
-    {
-        const ZC z = make_zc((f16)(float)(1 << (BITS - 1)));
-        #pragma unroll
-        for (int q = 0; q < 4; q++) zc[q] = z;
-    }
-    f16x2 p[16];
-    dequant_super<BITS>(lw.w, zc, p);
-    #pragma unroll
-    for (int q = 0; q < 4; q++)
-    {
-        if (q < nvalid)
-        {
-            const f16x8 b = {p[4 * q].x, p[4 * q].y, p[4 * q + 1].x, p[4 * q + 1].y, p[4 * q + 2].x, p[4 * q + 2].y, p[4 * q + 3].x, p[4 * q + 3].y};
-            f16x8 a;
-            if constexpr (PRE) a = pre[q]; else a = *(const f16x8*)(arow + q * 32);
-            const f32x4 part = mfma_16x16x32_f16(a, b, zero4);
-            #pragma unroll
-            for (int i = 0; i < 4; i++) acc[i] = fmaf(s[q], part[i], acc[i]);
-        }
-    }
-}
-#endif
 
 DEV const void* ptr_of(u32 lo, u32 hi) { return (const void*)global_ptr_of(lo, hi); }
 
@@ -719,7 +589,7 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
     auto head = [&](auto bits_tag, auto nb_tag) {
         constexpr int BITS = decltype(bits_tag)::value;
         constexpr int NB = decltype(nb_tag)::value;
-        constexpr int D = LeanDepth<BITS, S>::v;
+        constexpr int D = lean_depth(BITS, S);
         constexpr int DA = D - NB;
         constexpr size_t STEP = 64 * BITS;
         // (WALK without ROWS = the pair geometry whose 4 waves per tile take their share in up to three register loads: K = 8192 at 2-3 bits,
@@ -727,7 +597,7 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
         constexpr bool PAIR_LOADS = (S == 4 || S == 8) && PAIR && !ROWS && WALK;
         constexpr bool PASSES = !XMEM && (S == 16 || (S == 8 && NSLOTS == 1 && !PAIR && !ROWS && LEAN_S8_PASSES > 1 && BITS <= LEAN_S8_PASS_BITS) ||
                                           (PAIR_LOADS && BITS <= LEAN_S8_PASS_BITS) || LOADS);   // (what lean_plan_matrix plans)
-        constexpr bool RING = PASSES && LEAN_PASS_RING && BITS <= LEAN_S8_PASS_BITS;      // (wider items: a whole load at a time, the round-4 loop)
+        constexpr bool RING = PASSES && BITS <= LEAN_S8_PASS_BITS;      // (wider items: a whole load at a time, the round-4 loop)
         constexpr bool MANY_LOADS = S == 16 || PAIR_LOADS || LOADS;                          // shares of more than two register loads (the 70B pair: up to three)
         LaneWords<BITS> a[DA > 0 ? DA : 1], b[NB > 0 ? NB : 1], bt;
         const int nA = n - NB;
@@ -788,7 +658,7 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
         auto item = [&](const LaneWords<BITS>& w, int q) {
             if (R.uni) lean_item_uniform<BITS, GPTQ>(w, R.cx, R.chunk0 + 4 * q, R.g0 + ((4 * q + R.gphase) >> R.gshift), lane, acc);
             else lean_item_general<BITS, GPTQ>(w, R.cx, R.chunk0 + 4 * q, 4 * q, R.g0, R.gshift, R.gphase, 4, lane, acc);
-            if (LEAN_ITEM_FENCE) sched_fence();
+            sched_fence();                                             // (register pressure: the compiler must not interleave items)
         };
         // (shares of several register loads; returns true when it took the share)
         auto ring_passes = [&](auto on_tag) -> bool {
@@ -832,19 +702,7 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
             }
             else return false;
         };
-        if (LEAN_KILL & 8)
-        {
-            // timing experiment: the loads stay, the decode is an xor (what does the launch cost without the decode's VALU work?)
-            u32 xr = 0;
-            #pragma unroll
-            for (int q = 0; q < DA; q++) if (q < nA) { for (int e = 0; e < BITS; e++) xr ^= a[q].w[e]; }
-            #pragma unroll
-            for (int q = 0; q < NB; q++) { for (int e = 0; e < BITS; e++) xr ^= b[q].w[e]; }
-            if (tail_nv) for (int e = 0; e < BITS; e++) xr ^= bt.w[e];
-            acc[0] = __builtin_bit_cast(float, xr & 0x3fffffffu) + (float)R.cx.x_lds[lane] + (float)R.cx.sc_lds[lane & 15];
-        }
-        else if (LEAN_KILL & 1) { }
-        else if constexpr (XMEM)
+        if constexpr (XMEM)
         {
             // a ring of LEAN_XMEM_AHEAD items' A operands.  EVERY request is unconditional (an item the wave does not have
             // requests one 16-byte line, the same for all lanes): the compiler's count of the requests in flight stays exact, so
@@ -864,15 +722,6 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
         else if (ring_passes(std::integral_constant<bool, RING && NB == 0>())) { }
         else
         {
-#if LEAN_REPEAT
-            // timing experiment (results are WRONG: every sum is taken LEAN_REPEAT times): the decode of the wave's share runs again
-            // on the same registers -- the further passes find their code in the instruction cache and their data landed, so what they
-            // add is the decode's pure execution time (profiles/history/r05_repeat_experiment.txt)
-            u32 reps_ = LEAN_REPEAT; pin_scalar(reps_);
-            #pragma nounroll
-            for (u32 rep_ = 0; rep_ < reps_; rep_++)
-            {
-#endif
             #pragma unroll
             for (int q = 0; q < DA; q++) if (q < nA) item(a[q], q);
             if constexpr (NB > 0)
@@ -880,24 +729,18 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
                 #pragma unroll
                 for (int q = 0; q < NB; q++) item(b[q], nA + q);
             }
-#if LEAN_REPEAT
-            }
-#endif
         }
         // more items than the wave's registers hold (K = 28672 split over 16 waves: 14-15 items of 3 bits): further passes of D
         // items, each its own round trip -- only the 16-wave geometry, the last one the host tries, plans such shares
         if constexpr (PASSES && NB == 0 && !RING)
         {
-            if (!(LEAN_KILL & 9))
+            #pragma nounroll
+            for (int q0 = D; q0 < n; q0 += D)
             {
-                #pragma nounroll
-                for (int q0 = D; q0 < n; q0 += D)
-                {
-                    #pragma unroll
-                    for (int q = 0; q < D; q++) if (q0 + q < n) load_lane_words<BITS>(wptr + (size_t)(q0 + q) * STEP, lane, a[q]);
-                    #pragma unroll
-                    for (int q = 0; q < D; q++) if (q0 + q < n) item(a[q], q0 + q);
-                }
+                #pragma unroll
+                for (int q = 0; q < D; q++) if (q0 + q < n) load_lane_words<BITS>(wptr + (size_t)(q0 + q) * STEP, lane, a[q]);
+                #pragma unroll
+                for (int q = 0; q < D; q++) if (q0 + q < n) item(a[q], q0 + q);
             }
         }
         if constexpr (XMEM)
@@ -917,10 +760,10 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
     // a share of at least NB and at most D items takes the pipelined form
     auto head_bits = [&](auto bits_tag) {
         constexpr int BITS = decltype(bits_tag)::value;
-        constexpr int NB = LeanTail<BITS, S>::v;
+        constexpr int D = lean_depth(BITS, S), NB = lean_tail(BITS, S);
         if constexpr (NB > 0 && !ROWS && !XMEM)
         {
-            if (n >= NB && n <= LeanDepth<BITS, S>::v && pipe_on) { head(bits_tag, std::integral_constant<int, NB>()); return; }
+            if (n >= NB && n <= D && pipe_on) { head(bits_tag, std::integral_constant<int, NB>()); return; }
         }
         head(bits_tag, std::integral_constant<int, 0>());
     };
@@ -944,12 +787,8 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
         case 8: head_bits(std::integral_constant<int, 8>()); break;
         case 6: head_bits(std::integral_constant<int, 6>()); break;
         case 5: head_bits(std::integral_constant<int, 5>()); break;
-#if LEAN_LOWBITS
         case 3: head_bits(std::integral_constant<int, 3>()); break;
         default: head_bits(std::integral_constant<int, 2>()); break;
-#else
-        default: break;
-#endif
     }
     const int M = R.M;
     const u32 flags = R.flags;
@@ -1040,7 +879,7 @@ DEV void lean_body(const LeanArgs& args, const int by, const LeanDyn* const dyn 
             return v;
         };
         float sq = 0.0f;
-        if (ep_on && !(LEAN_KILL & 4))
+        if (ep_on)
         {
             f16 y;
             if constexpr (MOE_SUM)
@@ -1257,7 +1096,7 @@ static u32 lean_plan_matrix(const QMatrix* qm, int S, int M, bool norm, LeanWave
             }
             if (shift < 0 || c0 > 0xFFFF || c_end - c0 > 0xFFFF || g_lo > 0xFFFF || g_hi - g_lo + 1 > 0xFFFF) return 0;
             // what the kernel's straight-line staging copies (stage_copies); ROWS: the rows are staged by the workgroup, any length
-            // (XMEM: no staged activations -- any M <= 16, any slice; one pass only: the ring of A operands covers LeanDepth items)
+            // (XMEM: no staged activations -- any M <= 16, any slice; one pass only: the ring of A operands covers lean_depth() items)
             if ((g_hi - g_lo + 1) > sc_rows_max || (!rows_mode && !xmem && ((c_end - c0) * 4 > 64 * ((S == 4 && passes > 1) ? LEAN_X_PIECES_PAIR_LOADS : LEAN_X_PIECES_BASE) || M > 4))) return 0;
             if (xmem && n > lean_depth(r.bits, S)) return 0;
             const bool uni = shift >= 2 && (phase & 3) == 0;                   // the four chunks of every full item share a group
@@ -1281,52 +1120,93 @@ static u32 lean_plan_matrix(const QMatrix* qm, int S, int M, bool norm, LeanWave
     return lds_total ? lds_total : 16u;
 }
 
-#define LEAN_FOR_EACH_GEOMETRY(X, OCC) X(8, 1, false, OCC) X(16, 1, false, OCC) X(8, 2, false, OCC) X(8, 2, true, OCC) X(4, 2, true, OCC)
-#define LEAN_FOR_EACH_ROWS_GEOMETRY(X) X(8, 1, false, false) X(16, 1, false, false) X(8, 2, false, true) X(8, 2, true, true)
-#define LEAN_FOR_EACH_XMEM_GEOMETRY(X) X(8, 1, false) X(16, 1, false) X(8, 2, false) X(8, 2, true)
 // register budget: 6 waves per SIMD (80 registers: no spills on the common paths, three 8-wave workgroups per CU).  4 and 8
 // were built side by side during the round and measured (4 slower; 8 equal within noise once gate|up used 8-wave workgroups,
-// with spills): tools/build_variant.sh -DLEAN_OCC_DEFAULT=... rebuilds them
-#ifndef LEAN_OCC_DEFAULT
+// with spills)
 #define LEAN_OCC_DEFAULT 6
-#endif
 // the several-loads pair (70B gate|up): 80 registers as well -- three 8-wave workgroups per CU (53 KB of LDS each); at 128 registers
-// (two per CU) the launch takes what the 16-wave geometry took (59 us: gpurun r08a)
-#ifndef LEAN_PAIR_LOADS_OCC
+// (two per CU) the launch takes what the 16-wave geometry took (59 us)
 #define LEAN_PAIR_LOADS_OCC LEAN_OCC_DEFAULT
-#endif
+
+// ---- host: the instantiations -------------------------------------------------------------------------------------------------
+// EVERY kernel this file builds, once: X(GPTQ, S, NSLOTS, PAIR, OCC, ROWS, WALK, DEP, XMEM, LOADS).  The attribute calls, the lookup by
+// plan and the launch all come from this list; OCC is not part of a plan (one register budget per geometry).
+#define LEAN_DENSE_KERNELS(X) \
+    /* <= 4 rows, and the same as a launch of an overlapped chain (DEP) */ \
+    X(false,  8, 1, false, LEAN_OCC_DEFAULT, false, false, false, false, false) X(false,  8, 1, false, LEAN_OCC_DEFAULT, false, false, true, false, false) \
+    X(false, 16, 1, false, LEAN_OCC_DEFAULT, false, false, false, false, false) X(false, 16, 1, false, LEAN_OCC_DEFAULT, false, false, true, false, false) \
+    X(false,  8, 2, false, LEAN_OCC_DEFAULT, false, false, false, false, false) X(false,  8, 2, false, LEAN_OCC_DEFAULT, false, false, true, false, false) \
+    X(false,  8, 2, true,  LEAN_OCC_DEFAULT, false, false, false, false, false) X(false,  8, 2, true,  LEAN_OCC_DEFAULT, false, false, true, false, false) \
+    X(false,  4, 2, true,  LEAN_OCC_DEFAULT, false, false, false, false, false) X(false,  4, 2, true,  LEAN_OCC_DEFAULT, false, false, true, false, false) \
+    /* the pair whose 4 waves per tile take several register loads */ \
+    X(false,  4, 2, true,  LEAN_PAIR_LOADS_OCC, false, true, false, false, false) X(true,  4, 2, true,  LEAN_PAIR_LOADS_OCC, false, true, false, false, false) \
+    X(true,   8, 1, false, 6, false, false, false, false, false) X(true,   8, 1, false, 6, false, false, true, false, false) \
+    X(true,  16, 1, false, 6, false, false, false, false, false) X(true,  16, 1, false, 6, false, false, true, false, false) \
+    X(true,   8, 2, false, 6, false, false, false, false, false) X(true,   8, 2, false, 6, false, false, true, false, false) \
+    X(true,   8, 2, true,  6, false, false, false, false, false) X(true,   8, 2, true,  6, false, false, true, false, false) \
+    X(true,   4, 2, true,  6, false, false, false, false, false) X(true,   4, 2, true,  6, false, false, true, false, false) \
+    /* ROWS: the two-tile geometries walk */ \
+    X(false,  8, 1, false, 4, true, false, false, false, false) X(true,   8, 1, false, 4, true, false, false, false, false) \
+    X(false, 16, 1, false, 4, true, false, false, false, false) X(true,  16, 1, false, 4, true, false, false, false, false) \
+    X(false,  8, 2, false, 4, true, true,  false, false, false) X(true,   8, 2, false, 4, true, true,  false, false, false) \
+    X(false,  8, 2, true,  4, true, true,  false, false, false) X(true,   8, 2, true,  4, true, true,  false, false, false) \
+    /* LOADS */ \
+    X(false,  8, 2, false, 4, true, true,  false, false, true) \
+    /* XMEM */ \
+    X(false,  8, 1, false, 4, false, false, false, true, false) X(true,   8, 1, false, 4, false, false, false, true, false) \
+    X(false, 16, 1, false, 4, false, false, false, true, false) X(true,  16, 1, false, 4, false, false, false, true, false) \
+    X(false,  8, 2, false, 4, false, false, false, true, false) X(true,   8, 2, false, 4, false, false, false, true, false) \
+    X(false,  8, 2, true,  4, false, false, false, true, false) X(true,   8, 2, true,  4, false, false, false, true, false)
+// the grouped-expert kernels: X(S, NSLOTS, PAIR, OCC, WALK)
+#define LEAN_MOE_KERNELS(X) \
+    X(4, 2, true, LEAN_OCC_DEFAULT, false) X(4, 2, true, LEAN_PAIR_LOADS_OCC, true) X(8, 2, true, LEAN_OCC_DEFAULT, false) X(8, 2, true, LEAN_OCC_DEFAULT, true) \
+    X(8, 1, false, LEAN_OCC_DEFAULT, false) X(16, 1, false, LEAN_OCC_DEFAULT, false)
+
+// what a plan asks for, packed: the case labels of the lookups below (two entries of a list with one key do not compile)
+constexpr u32 lean_key(bool gptq, int S, int nslots, bool pair, bool rows, bool walk, bool dep, bool xmem, bool loads)
+{
+    return (u32)S | (u32)nslots << 8 | (u32)gptq << 16 | (u32)pair << 17 | (u32)rows << 18 | (u32)walk << 19 | (u32)dep << 20 | (u32)xmem << 21 | (u32)loads << 22;
+}
+typedef void (*LeanKernelFn)(const LeanArgs);
+typedef void (*LeanMoeKernelFn)(const LeanArgs*, const LeanDyn);
+// nullptr: no such kernel -- the launch is declined
+static LeanKernelFn lean_dense_kernel(u32 key)
+{
+    switch (key)
+    {
+#define LEAN_CASE(G, S, NS, P, OCC, R, W, D, XM, L) case lean_key(G, S, NS, P, R, W, D, XM, L): return qgemv_lean_kernel<G, S, NS, P, OCC, R, W, D, XM, L>;
+        LEAN_DENSE_KERNELS(LEAN_CASE)
+#undef LEAN_CASE
+        default: return nullptr;
+    }
+}
+static LeanMoeKernelFn lean_moe_kernel(int S, int nslots, bool pair, bool walk)
+{
+    switch (lean_key(false, S, nslots, pair, false, walk, false, false, false))
+    {
+#define LEAN_CASE(S, NS, P, OCC, W) case lean_key(false, S, NS, P, false, W, false, false, false): return qgemv_lean_moe_kernel<S, NS, P, OCC, W>;
+        LEAN_MOE_KERNELS(LEAN_CASE)
+#undef LEAN_CASE
+        default: return nullptr;
+    }
+}
 
 static void lean_attrs()
 {
     static bool attr[EXL2_MAX_DEVICES] = {false};
     if (!exl2_first_on_device(attr)) return;
-#define LEAN_ATTR(S, NS, P, OCC) \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<false, S, NS, P, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<false, S, NS, P, OCC, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LEAN_FOR_EACH_GEOMETRY(LEAN_ATTR, LEAN_OCC_DEFAULT)
-#undef LEAN_ATTR
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<false, 4, 2, true, LEAN_PAIR_LOADS_OCC, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<true, 4, 2, true, LEAN_PAIR_LOADS_OCC, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#define LEAN_ATTR(S, NS, P, OCC) \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<true, S, NS, P, OCC>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<true, S, NS, P, OCC, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LEAN_FOR_EACH_GEOMETRY(LEAN_ATTR, 6)
-#undef LEAN_ATTR
-#define LEAN_ATTR(S, NS, P, W) \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<false, S, NS, P, 4, true, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<true, S, NS, P, 4, true, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LEAN_FOR_EACH_ROWS_GEOMETRY(LEAN_ATTR)
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<false, 8, 2, false, 4, true, true, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#undef LEAN_ATTR
-#define LEAN_ATTR(S, NS, P) \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<false, S, NS, P, 4, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<true, S, NS, P, 4, false, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    LEAN_FOR_EACH_XMEM_GEOMETRY(LEAN_ATTR)
+#define LEAN_ATTR(G, S, NS, P, OCC, R, W, D, XM, L) \
+    (void)hipFuncSetAttribute((const void*)qgemv_lean_kernel<G, S, NS, P, OCC, R, W, D, XM, L>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    LEAN_DENSE_KERNELS(LEAN_ATTR)
 #undef LEAN_ATTR
 }
 
 // what qgemv_lean_launch hands out instead of launching (FlatIn.lean_export): the argument block and the geometry it chose
 struct LeanExport { LeanArgs args; int S, nslots, pair, walk, grid_x; u32 lds; bool plain; };
+
+// the forms of a launch (lean_body) and one geometry the host tries for a form
+enum LeanForm { LEAN_FORM_PLAIN, LEAN_FORM_ROWS, LEAN_FORM_XMEM, LEAN_FORM_LOADS };      // <= 4 rows in wave-private slices | ROWS | XMEM | LOADS
+struct LeanCand { int S, slots, passes; u32 budget; };             // 0 = the tile count as it stands | the geometry's default (lean_plan_matrix) | LEAN_LDS_BUDGET per 8 waves
 
 static int lean_cus()
 {
@@ -1378,102 +1258,94 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
     if (!in.pair && in.n_mats == 1 && in.ss_out && max_tiles > LEAN_MAX_PART) nslots = 2;
     if (const char* e = getenv("EXL2_LEAN_TPW")) { const int v = atoi(e); if (!in.pair && in.n_mats == 1 && (v == 1 || v == 2)) nslots = v; }
     if (const char* e = getenv("EXL2_LEAN_S16")) { if (atoi(e) && nslots == 1 && in.n_mats <= 2) S = 16; }
-    // candidates, in order: a one-row pair tries 4 waves per tile first (8-wave workgroups: three per CU at 6 waves per SIMD, so
-    // the 688 workgroups of a 7B gate|up launch are resident at once; with 16-wave workgroups a quarter of them starts when
-    // the first ones have finished: profiles/history/r03_trace_lean_v6.txt, workgroup entry p90 9.5 us)
-    int cand[3] = {0, 0, 0}, n_cand = 0;
+    const int xmem_on = []() { const char* e = getenv("EXL2_LEAN_XMEM"); return e ? atoi(e) : 1; }();     // (read per launch build: tests switch it)
+    // A/B switches of the candidate lists below (read once)
     static const int pair4 = []() { const char* e = getenv("EXL2_LEAN_PAIR4"); return e ? atoi(e) : 1; }();
-    int cand_passes[3] = {0, 0, 0};                                    // (0 = the geometry's default: lean_plan_matrix)
-    u32 cand_budget[3] = {0, 0, 0};                                    // (0 = LEAN_LDS_BUDGET per 8 waves)
-    if (in.pair && in.M == 1 && pair4) cand[n_cand++] = 4;
-    // a pair whose K is too long for ONE register load of its 4 waves per tile (70B: K = 8192 at 2-3 bits = 19 items per wave): two
-    // loads (the ring of the 8-wave q|k|v launches) and a 64 KB budget -- two 8-wave workgroups per CU, 512 of the 1792 resident
-    // at once -- before the 16-wave workgroup that is alone on its CU (seven rounds of 256: profiles/history/r05_70b_kernel_stats.csv)
     static const int pair4_passes = []() { const char* e = getenv("EXL2_LEAN_PAIR4_PASSES"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > LEAN_MAX_PASSES ? LEAN_MAX_PASSES : v); }();
     static const u32 pair4_budget = []() { const char* e = getenv("EXL2_LEAN_PAIR4_BUDGET_KB"); const int v = e ? atoi(e) : 64; return (u32)(v < 16 ? 16 : (v > 150 ? 150 : v)) * 1024u; }();
-    if (in.pair && in.M == 1 && pair4 && pair4_passes > 1 && !in.a_tiled && !dep) { cand_passes[n_cand] = pair4_passes; cand_budget[n_cand] = pair4_budget; cand[n_cand++] = 4; }
-    cand[n_cand++] = S;
-    // several matrices in one launch (q|k|v) whose shares 8 waves cannot hold in ONE register load: two loads on 8 waves before 16
-    // waves -- a 16-wave workgroup is alone on its CU (80 registers x 4 waves per SIMD), so the 640 tiles of a 70B q|k|v launch ran
-    // as three rounds of 256; 8-wave workgroups are three per CU and all resident at once
     static const int s8_passes = []() { const char* e = getenv("EXL2_LEAN_S8_PASSES"); const int v = e ? atoi(e) : LEAN_S8_PASSES; return v < 1 ? 1 : (v > LEAN_S8_PASSES ? LEAN_S8_PASSES : v); }();
     const int s8_single = []() { const char* e = getenv("EXL2_LEAN_S8_SINGLE"); return e ? atoi(e) : 0; }();      // (A/B: the two-load 8-wave form for ONE matrix too -- down_proj)
-    if (!in.pair && nslots == 1 && S == 8 && (in.n_mats >= 2 || s8_single) && s8_passes > 1 && !rows_mode && !in.a_tiled) { cand_passes[n_cand] = s8_passes; cand[n_cand++] = 8; }
-    if (!in.pair && nslots == 1 && S == 8) cand[n_cand++] = 16;        // finer split of the tile
-    // ROWS geometries, in order: two tiles x 8 waves sharing the staged rows (16 waves per CU), one tile x 8, one tile x 16; pair (8 + 8)
-    // XMEM geometries (the rows do not fit / EXL2_LEAN_XMEM=2): one tile x 8, one tile x 16; pair (8 + 8)
-    // the weighted sum of two experts' down projections (MOE_SUM): 8 waves per expert's tile, up to LEAN_MAX_PASSES ring loads each,
-    // the 16-wave workgroup alone on its CU (two activation slices + two sets of scale rows: 86 KB at Mixtral's K = 14336)
-    if (in.pair_sum) { n_cand = 1; cand[0] = 8; cand_passes[0] = LEAN_MAX_PASSES; cand_budget[0] = 150u * 1024u; }
-    int cand_slots[3] = {nslots, nslots, nslots};
-    const int xmem_on = []() { const char* e = getenv("EXL2_LEAN_XMEM"); return e ? atoi(e) : 1; }();     // (read per launch build: tests switch it)
+    const int S0 = S, nslots0 = nslots;
+    auto candidates = [&](LeanForm form) {
+        std::vector<LeanCand> c;
+        switch (form)
+        {
+        case LEAN_FORM_PLAIN:
+        {
+            // the weighted sum of two experts' down projections (MOE_SUM): 8 waves per expert's tile, up to LEAN_MAX_PASSES ring loads each,
+            // the 16-wave workgroup alone on its CU (two activation slices + two sets of scale rows: 86 KB at Mixtral's K = 14336)
+            if (in.pair_sum) { c.push_back({8, 0, LEAN_MAX_PASSES, 150u * 1024u}); break; }
+            // a one-row pair tries 4 waves per tile first (8-wave workgroups: three per CU at 6 waves per SIMD, so
+            // the 688 workgroups of a 7B gate|up launch are resident at once; with 16-wave workgroups a quarter of them starts when
+            // the first ones have finished: profiles/history/r03_trace_lean_v6.txt, workgroup entry p90 9.5 us)
+            if (in.pair && in.M == 1 && pair4) c.push_back({4, 0, 0, 0u});
+            // a pair whose K is too long for ONE register load of its 4 waves per tile (70B: K = 8192 at 2-3 bits = 19 items per wave): two
+            // loads (the ring of the 8-wave q|k|v launches) and a 64 KB budget -- two 8-wave workgroups per CU, 512 of the 1792 resident
+            // at once -- before the 16-wave workgroup that is alone on its CU (seven rounds of 256: profiles/history/r05_70b_kernel_stats.csv)
+            if (in.pair && in.M == 1 && pair4 && pair4_passes > 1 && !in.a_tiled && !dep) c.push_back({4, 0, pair4_passes, pair4_budget});
+            c.push_back({S0, 0, 0, 0u});
+            // several matrices in one launch (q|k|v) whose shares 8 waves cannot hold in ONE register load: two loads on 8 waves before 16
+            // waves -- a 16-wave workgroup is alone on its CU (80 registers x 4 waves per SIMD), so the 640 tiles of a 70B q|k|v launch ran
+            // as three rounds of 256; 8-wave workgroups are three per CU and all resident at once
+            if (!in.pair && nslots0 == 1 && S0 == 8 && (in.n_mats >= 2 || s8_single) && s8_passes > 1 && !rows_mode && !in.a_tiled) c.push_back({8, 0, s8_passes, 0u});
+            if (!in.pair && nslots0 == 1 && S0 == 8) c.push_back({16, 0, 0, 0u});        // finer split of the tile
+            break;
+        }
+        case LEAN_FORM_ROWS:                                        // two tiles x 8 waves sharing the staged rows (16 waves per CU), one tile x 8, one tile x 16; pair (8 + 8)
+            if (in.pair) { c.push_back({8, 2, 0, 0u}); break; }
+            // (up to 8 rows the staged rows leave room for two 8-wave workgroups per CU: one tile per workgroup, the whole grid
+            // resident; from 9 rows up one workgroup per CU anyway: two tiles per unit, the workgroup walks -- profiles/history/r04_rows_sweep*.txt)
+            if (in.M >= 9 && !(in.ss_out && (max_tiles + 1) / 2 > LEAN_MAX_PART) && max_tiles >= 2) c.push_back({8, 2, 0, 0u});
+            c.push_back({8, 1, 0, 0u});
+            c.push_back({16, 1, 0, 0u});                               // (K = 11008: a tile's share does not fit 8 waves' registers)
+            break;
+        case LEAN_FORM_XMEM:                                        // (the rows do not fit / EXL2_LEAN_XMEM=2): one tile x 8, one tile x 16; pair (8 + 8)
+            if (in.pair || (in.ss_out && max_tiles > LEAN_MAX_PART)) { c.push_back({8, 2, 0, 0u}); break; }
+            c.push_back({8, 1, 0, 0u});
+            c.push_back({16, 1, 0, 0u});
+            break;
+        case LEAN_FORM_LOADS:                                       // two tiles x 8 waves, shares of up to LEAN_MAX_PASSES register loads
+            c.push_back({8, 2, LEAN_MAX_PASSES, 0u});
+            break;
+        }
+        return c;
+    };
     bool xmem = false;
     u32 rows_bytes = 0, slot_bytes = 0;
     bool planned = false;
     int planned_passes = 0;
-    const int nslots0 = nslots;
-    const int plain_cand[3] = {cand[0], cand[1], cand[2]};
-    const int plain_passes[3] = {cand_passes[0], cand_passes[1], cand_passes[2]};
-    const u32 plain_budget[3] = {cand_budget[0], cand_budget[1], cand_budget[2]};
-    const int plain_n = n_cand;
-    auto plan = [&](int form) {                                      // 0: <= 4 rows; 1: ROWS; 2: XMEM
-        n_cand = plain_n;
-        for (int i = 0; i < 3; i++) { cand[i] = plain_cand[i]; cand_slots[i] = nslots0; cand_passes[i] = form ? 0 : plain_passes[i]; cand_budget[i] = form ? 0u : plain_budget[i]; }
-        if (form == 3)                                              // LOADS: two tiles x 8 waves, shares of up to LEAN_MAX_PASSES register loads
-        {
-            n_cand = 1; cand[0] = 8; cand_slots[0] = 2; cand_passes[0] = LEAN_MAX_PASSES;
-        }
-        else if (form == 1)
-        {
-            n_cand = 0;
-            if (in.pair) { cand[n_cand] = 8; cand_slots[n_cand++] = 2; }
-            else
-            {
-                // (up to 8 rows the staged rows leave room for two 8-wave workgroups per CU: one tile per workgroup, the whole grid
-                // resident; from 9 rows up one workgroup per CU anyway: two tiles per unit, the workgroup walks -- profiles/history/r04_rows_sweep*.txt)
-                if (in.M >= 9 && !(in.ss_out && (max_tiles + 1) / 2 > LEAN_MAX_PART) && max_tiles >= 2) { cand[n_cand] = 8; cand_slots[n_cand++] = 2; }
-                cand[n_cand] = 8; cand_slots[n_cand++] = 1;
-                cand[n_cand] = 16; cand_slots[n_cand++] = 1;               // (K = 11008: a tile's share does not fit 8 waves' registers)
-            }
-        }
-        else if (form == 2)
-        {
-            n_cand = 0;
-            if (in.pair) { cand[n_cand] = 8; cand_slots[n_cand++] = 2; }
-            else if (in.ss_out && max_tiles > LEAN_MAX_PART) { cand[n_cand] = 8; cand_slots[n_cand++] = 2; }
-            else
-            {
-                cand[n_cand] = 8; cand_slots[n_cand++] = 1;
-                cand[n_cand] = 16; cand_slots[n_cand++] = 1;
-            }
-        }
+    auto plan = [&](LeanForm form) {
+        const std::vector<LeanCand> cand = candidates(form);
+        const int n_cand = (int)cand.size();
+        const bool staged_rows = form == LEAN_FORM_ROWS || form == LEAN_FORM_LOADS;
         // ROWS: the workgroup's shared copy of the M rows, in front of the waves' own (scale-row) areas
-        rows_bytes = (form == 1 || form == 3) ? al16((u32)in.M * (u32)(K + 8) * 2u) : 0u;
+        rows_bytes = staged_rows ? al16((u32)in.M * (u32)(K + 8) * 2u) : 0u;
         // (second round: a split that fits only with the whole LDS of a CU -- 2-4 rows of a K = 11008 matrix -- is still better
         // than leaving the chain: the decoder would fall back to the module-by-module route for EVERY launch)
         for (int ci = 0; ci < 2 * n_cand && !planned; ci++)
         {
-            S = cand[ci % n_cand];
-            if (form) nslots = cand_slots[ci % n_cand];
-            const u32 budget = (form == 1 || form == 3) ? 158u * 1024u : (ci < n_cand ? (cand_budget[ci] ? cand_budget[ci] : LEAN_LDS_BUDGET * (u32)((S * nslots + 7) / 8)) : 150u * 1024u);
+            const LeanCand& c = cand[ci % n_cand];
+            S = c.S;
+            if (c.slots) nslots = c.slots;
+            const u32 budget = staged_rows ? 158u * 1024u : (ci < n_cand ? (c.budget ? c.budget : LEAN_LDS_BUDGET * (u32)((S * nslots + 7) / 8)) : 150u * 1024u);
             if (in.n_mats * S > LEAN_RECORDS) continue;
             bool ok = true;
             slot_bytes = 0;
             for (int j = 0; j < in.n_mats && ok; j++)
             {
-                const u32 b = lean_plan_matrix(in.qm[j], S, in.M, in.a_mode == A_NORM_PRE, a.wave + j * S, form == 1 || form == 3, form == 2, cand_passes[ci % n_cand], form == 3 ? 128 : 64);
+                const u32 b = lean_plan_matrix(in.qm[j], S, in.M, in.a_mode == A_NORM_PRE, a.wave + j * S, staged_rows, form == LEAN_FORM_XMEM, c.passes, form == LEAN_FORM_LOADS ? 128 : 64);
                 if (!b) ok = false;
                 if (b > slot_bytes) slot_bytes = b;
             }
             planned = ok && rows_bytes + (u32)nslots * slot_bytes + (u32)(S * nslots) * (u32)in.M * 64u <= budget;
-            if (planned) planned_passes = cand_passes[ci % n_cand];
+            if (planned) planned_passes = c.passes;
         }
-        xmem = planned && form == 2;
+        xmem = planned && form == LEAN_FORM_XMEM;
     };
-    if (in.a_tiled) plan(2);                                       // (only the XMEM form reads that layout)
-    else if (!rows_mode) plan(0);
-    else if (xmem_on >= 2) { plan(2); if (!planned) plan(1); }
-    else { plan(1); if (!planned && xmem_on >= 1) plan(2); }
+    if (in.a_tiled) plan(LEAN_FORM_XMEM);                          // (only the XMEM form reads that layout)
+    else if (!rows_mode) plan(LEAN_FORM_PLAIN);
+    else if (xmem_on >= 2) { plan(LEAN_FORM_XMEM); if (!planned) plan(LEAN_FORM_ROWS); }
+    else { plan(LEAN_FORM_ROWS); if (!planned && xmem_on >= 1) plan(LEAN_FORM_XMEM); }
     if (!planned) return 1;
     // one row, one matrix, a 16-wave workgroup per tile and more tiles than CUs (two rounds of workgroups that are alone on their CU):
     // the LOADS form -- two tiles per workgroup over ONE staged copy of the row, one round -- where it plans
@@ -1482,9 +1354,9 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
         max_tiles > lean_cus() && !(in.ss_out && (max_tiles + 1) / 2 > LEAN_MAX_PART))
     {
         planned = false;
-        plan(3);
+        plan(LEAN_FORM_LOADS);
         if (planned) { rows_mode = true; rows_loads = true; }
-        else { plan(0); if (!planned) return 1; }
+        else { plan(LEAN_FORM_PLAIN); if (!planned) return 1; }      // (plain candidates keep the tile count: the declined attempt's two)
     }
     const int wgs = in.pair ? max_tiles : (max_tiles + nslots - 1) / nslots;
     if (in.ss_out && wgs > LEAN_MAX_PART) return 1;
@@ -1550,49 +1422,17 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
     }
     if (in.plan_only) { if (wgs_out) *wgs_out = wgs; return 0; }                      // a caller asking whether this shape is taken (modules.hip)
     if (getenv("EXL2_LEAN_PLAN_ONLY")) { if (wgs_out) *wgs_out = wgs; return 0; }     // test hook: the host plan without the launch (results undefined)
-    int launched = 0;                                                                  // a plan no instantiation below matches must not pass for a launch
-    const bool gptq = q0->is_gptq;
-    const int occ = LEAN_OCC_DEFAULT;
-#define LEAN_LAUNCH(...) do { launched++; LAUNCH(__VA_ARGS__); } while (0)
-    if (rows_loads) LEAN_LAUNCH((qgemv_lean_kernel<false, 8, 2, false, 4, true, true, false, false, true>), grid, block, lds, stream, a);
-#define LEAN_GO(SS, NS, P, W) \
-    if (!rows_loads && rows_mode && !xmem && !gptq && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<false, SS, NS, P, 4, true, W>), grid, block, lds, stream, a); \
-    if (rows_mode && !xmem && gptq && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<true, SS, NS, P, 4, true, W>), grid, block, lds, stream, a);
-    LEAN_FOR_EACH_ROWS_GEOMETRY(LEAN_GO)
-#undef LEAN_GO
-#define LEAN_GO(SS, NS, P) \
-    if (xmem && !gptq && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<false, SS, NS, P, 4, false, false, false, true>), grid, block, lds, stream, a); \
-    if (xmem && gptq && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<true, SS, NS, P, 4, false, false, false, true>), grid, block, lds, stream, a);
-    LEAN_FOR_EACH_XMEM_GEOMETRY(LEAN_GO)
-#undef LEAN_GO
-    const bool pair_loads = in.pair && S == 4 && planned_passes > 1 && !rows_mode && !xmem && !dep;      // (the several-register-loads pair: its own instantiation)
-    if (pair_loads && !gptq) LEAN_LAUNCH((qgemv_lean_kernel<false, 4, 2, true, LEAN_PAIR_LOADS_OCC, false, true>), grid, block, lds, stream, a);
-    if (pair_loads && gptq) LEAN_LAUNCH((qgemv_lean_kernel<true, 4, 2, true, LEAN_PAIR_LOADS_OCC, false, true>), grid, block, lds, stream, a);
-#define LEAN_GO(SS, NS, P, OCC) \
-    if (!pair_loads && !rows_mode && !xmem && !dep && !gptq && occ == OCC && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<false, SS, NS, P, OCC>), grid, block, lds, stream, a); \
-    if (!rows_mode && dep && !gptq && occ == OCC && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<false, SS, NS, P, OCC, false, false, true>), grid, block, lds, stream, a);
-    LEAN_FOR_EACH_GEOMETRY(LEAN_GO, LEAN_OCC_DEFAULT)
-#undef LEAN_GO
-#define LEAN_GO(SS, NS, P, OCC) \
-    if (!pair_loads && !rows_mode && !xmem && !dep && gptq && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<true, SS, NS, P, OCC>), grid, block, lds, stream, a); \
-    if (!rows_mode && dep && gptq && S == SS && nslots == NS && (in.pair != 0) == P) LEAN_LAUNCH((qgemv_lean_kernel<true, SS, NS, P, OCC, false, false, true>), grid, block, lds, stream, a);
-    LEAN_FOR_EACH_GEOMETRY(LEAN_GO, 6)
-#undef LEAN_GO
-#undef LEAN_LAUNCH
-    if (launched != 1)
-    {
-        fprintf(stderr, "[exl2] qgemv_lean_launch: plan (S=%d slots=%d pair=%d rows=%d xmem=%d dep=%d gptq=%d) matched %d instantiations\n",
-                S, nslots, in.pair, (int)rows_mode, (int)xmem, (int)dep, (int)gptq, launched);
-        return launched ? -3 : 1;                   // nothing launched: declined (the caller's fallback runs); two: a dispatch bug
-    }
+    // the plan's key: ROWS kernels walk in their two-tile geometries, otherwise only the several-register-loads pair does
+    const bool rows = rows_mode && !xmem;
+    const bool pair_loads = in.pair && S == 4 && planned_passes > 1 && !rows_mode && !xmem && !dep;
+    const LeanKernelFn kernel = lean_dense_kernel(lean_key(q0->is_gptq, S, nslots, in.pair != 0, rows, rows ? nslots == 2 : pair_loads, dep, xmem, rows_loads));
+    if (!kernel) return 1;                                          // no such instantiation: declined (the caller's fallback runs)
+    LAUNCH(kernel, grid, block, lds, stream, a);
     if (wgs_out) *wgs_out = wgs;
     return 0;
 }
 
 // ---- grouped-expert launches (qgemv_lean.h) ---------------------------------------------------------------------------------------
-#define LEAN_FOR_EACH_MOE_GEOMETRY(X) X(4, 2, true, LEAN_OCC_DEFAULT, false) X(4, 2, true, LEAN_PAIR_LOADS_OCC, true) X(8, 2, true, LEAN_OCC_DEFAULT, false) \
-                                      X(8, 2, true, LEAN_OCC_DEFAULT, true) \
-                                      X(8, 1, false, LEAN_OCC_DEFAULT, false) X(16, 1, false, LEAN_OCC_DEFAULT, false)
 
 int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out_scale, int n_sel, LeanGroupPlan* gp, int r_stride, int mul)
 {
@@ -1646,11 +1486,7 @@ int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out
         gp->lds = slot_bytes * (u32)gp->nslots + (u32)(gp->S * gp->nslots) * 16u * 4u;
         if (gp->lds > 160u * 1024u) return 1;
     }
-    bool inst = false;
-#define LEAN_HAS(SS, NS, P, OCC, W) if (gp->S == SS && gp->nslots == NS && (gp->pair != 0) == P && (gp->walk != 0) == W) inst = true;
-    LEAN_FOR_EACH_MOE_GEOMETRY(LEAN_HAS)
-#undef LEAN_HAS
-    if (!inst) return 1;
+    if (!lean_moe_kernel(gp->S, gp->nslots, gp->pair != 0, gp->walk != 0)) return 1;
     gp->n_groups = n_groups; gp->n_sel = n_sel; gp->block_bytes = (int)sizeof(LeanArgs);
     gp->pair_sum = ins[0].pair_sum ? 1 : 0;
     gp->all_groups = r_stride != 0 ? 1 : 0;
@@ -1685,16 +1521,14 @@ int qgemv_lean_group_launch(const LeanGroupPlan* gp, void* stream, const LeanGro
     if (exl2_first_on_device(attr))
     {
 #define LEAN_ATTR(SS, NS, P, OCC, W) (void)hipFuncSetAttribute((const void*)qgemv_lean_moe_kernel<SS, NS, P, OCC, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        LEAN_FOR_EACH_MOE_GEOMETRY(LEAN_ATTR)
+        LEAN_MOE_KERNELS(LEAN_ATTR)
 #undef LEAN_ATTR
     }
     // (all_groups: blockIdx.y = expert, the blocks as planned -- workgroups of experts without a row leave at entry)
     const dim3 grid((unsigned)gp->grid_x, (unsigned)(gp->pair_sum ? 1 : (gp->all_groups ? gp->n_groups : gp->n_sel)), 1), block((unsigned)(gp->S * gp->nslots) * 64, 1, 1);
     const LeanArgs* const table = (const LeanArgs*)(gp->all_groups ? gp->table_src : gp->table_sel);
-    int launched = 0;
-#define LEAN_GO(SS, NS, P, OCC, W) \
-    if (gp->S == SS && gp->nslots == NS && (gp->pair != 0) == P && (gp->walk != 0) == W) { launched++; LAUNCH((qgemv_lean_moe_kernel<SS, NS, P, OCC, W>), grid, block, gp->lds, stream, table, dyn); }
-    LEAN_FOR_EACH_MOE_GEOMETRY(LEAN_GO)
-#undef LEAN_GO
-    return launched == 1 ? 0 : 1;
+    const LeanMoeKernelFn kernel = lean_moe_kernel(gp->S, gp->nslots, gp->pair != 0, gp->walk != 0);
+    if (!kernel) return 1;
+    LAUNCH(kernel, grid, block, gp->lds, stream, table, dyn);
+    return 0;
 }

@@ -31,9 +31,6 @@
 #define SAMPLE_THREADS 1024
 #define SAMPLE_KMAX 500
 #define SAMPLE_KPAD 512                // >= SAMPLE_KMAX + 2, a multiple of 8
-#ifndef SAMPLE_KILL
-#define SAMPLE_KILL 0                  // timing experiments (results are WRONG): 1 no candidate stages, 2 no ranking of the quick select's list
-#endif
 #define SAMPLE_LIST 1024               // quick select: entries at or above the lower bound it can hold (more: the radix passes)
 
 struct SampleArgs
@@ -310,8 +307,7 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
             {
                 my_key = lst_k[t]; my_i = lst_i[t];
                 u32 gt = 0, eq = 0, eq_hi = 0;
-                if (SAMPLE_KILL & 2) { gt = (u32)t; eq = 1; }
-                else for (u32 j = 0; j < L; j++)
+                for (u32 j = 0; j < L; j++)
                 {
                     const u32 kj = lst_k[j];
                     gt += kj > my_key;
@@ -460,7 +456,6 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
     // candidate over the stages.  The passes read 8 entries per round trip into registers (two 16-byte reads) and keep the
     // reference's order of every sum and comparison; the stack's top two values live in registers.
     int n = K;
-    if (SAMPLE_KILL & 1) { if (lead) { a.out_tokens[row] = cand_i[0]; a.out_probs[row] = cand_p[0]; } return; }
     auto load8 = [&](const float* arr, int i0, float (&v)[8]) {
         const f32x4 lo = *(const f32x4*)(arr + i0), hi = *(const f32x4*)(arr + i0 + 4);
         v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;

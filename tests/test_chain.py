@@ -569,7 +569,7 @@ DEEP_SPECS = {
 def test_gemm_chain_shares_of_several_register_loads(be, rows, spec_name, capfd, monkeypatch):
     """A wave's share beyond its registers (70B down_proj: K = 28672 on 16 waves) is decoded as a RING: item q of the next register
     load is requested as soon as item q of the current one is decoded.  Numerics against the oracle for 2, 3 and 4-bit shares of
-    two and three loads, one and three rows; the plan is checked to be the multi-load one (a wave with more items than LeanDepth)."""
+    two and three loads, one and three rows; the plan is checked to be the multi-load one (a wave with more items than lean_depth())."""
     k, spec = DEEP_SPECS[spec_name]
     if rows * k * 2 > 140 * 1024:
         pytest.skip("rows x K beyond one workgroup's LDS: the decoder serves such launches as smaller row groups")
@@ -730,8 +730,8 @@ def test_lean_kernel_identity_rows_equal_reconstruct(be, rows, spec_id):
     k, n = 1024, 96
     spec = [(5, 128, 128), (4, 128, 512), (4, 32, 256), (4, 64, 128)]
     if spec_id == "3_2_pairs":
-        # round 6: 3 / 2-bit items whose groups are chunk PAIRS (group size 64) take the scale on the pair's fp32 sum (LEAN_DUO);
-        # a g32 section of each width beside them (a scale per chunk, on the weights)
+        # round 6: 3 / 2-bit items whose groups are chunk PAIRS (group size 64) -- the shapes of the pair-scale experiment, which was
+        # measured and removed: they take a scale per chunk, on the weights, like the g32 section of each width beside them
         spec = [(4, 128, 128), (3, 64, 384), (3, 32, 128), (2, 64, 256), (2, 32, 128)]
     t, ref, w, h = _mk(be, k, n, spec, 77)
     be.ext.chain_route_counts(reset=True)                              # (a process-wide counter: other tests' launches are not this test's)
