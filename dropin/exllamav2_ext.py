@@ -120,6 +120,14 @@ if _fast is not None:
         _fast.note_write(x)
         return _e.rms_norm_(x, w, epsilon)
 
+    def head_norm(x, w, b, y, epsilon, rms):
+        _fast.note_write(y)
+        return _e.head_norm(x, w, b, y, epsilon, rms)
+
+    def head_norm_(x, w, b, epsilon, rms):
+        _fast.note_write(x)
+        return _e.head_norm_(x, w, b, epsilon, rms)
+
     def rope_(x, sin, cos, past_len, num_heads, head_dim, offsets, neox_style):
         _fast.note_write(x)
         return _e.rope_(x, sin, cos, past_len, num_heads, head_dim, offsets, neox_style)
@@ -136,6 +144,8 @@ else:
     gemm_half_q_half = _e.gemm_half_q_half
     rms_norm = _e.rms_norm
     rms_norm_ = _e.rms_norm_
+    head_norm = _e.head_norm
+    head_norm_ = _e.head_norm_
     rope_ = _e.rope_
     q_moe_mlp_forward_ = _e.q_moe_mlp_forward_
 
@@ -180,7 +190,7 @@ cache_rotate = _e.cache_rotate
 count_match = _e.count_match
 matrix_fp16_to_q4 = _e.matrix_fp16_to_q4
 matrix_q4_to_fp16 = _e.matrix_q4_to_fp16
-for _n in ("layer_norm", "layer_norm_", "head_norm", "head_norm_", "softcap_", "gen_mrope_pos_ids", "gemm_half_half_half",
+for _n in ("layer_norm", "layer_norm_", "softcap_", "gen_mrope_pos_ids", "gemm_half_half_half",
            "had_paley", "had_paley2", "pack_rows_4", "pack_columns", "quantize", "quantize_err", "quantize_range",
            "quantize_range_inplace", "sim_anneal", "logit_filter_exclusive",
            "dump_profile_results", "stloader_open_file", "stloader_close_file"):

@@ -34,6 +34,9 @@ PROTOTYPES = {
     # norm / rope / activation
     "exl2_rms_norm": (ci, [vp, vp, vp, cf, ci, ci, ci, ci, ci, vp]),
     "exl2_rope_qk": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp]),
+    "exl2_head_norm": (ci, [vp, vp, vp, vp, cf, ci, ci, ci, ci, vp]),
+    "exl2_head_norm_qk": (ci, [vp, vp, vp, vp, cf, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "exl2_head_norm_rope_qk": (ci, [vp, vp, vp, vp, cf, ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, ci, ci, vp]),
     "exl2_act_mul": (ci, [vp, vp, ci, ci, ci, vp, ci, vp]),
     # decode-loop utilities
     "exl2_embed_rows": (ci, [vp, vp, vp, ci, ci, ci, vp]),
@@ -67,6 +70,8 @@ PROTOTYPES = {
                                     vp, cll, vp, ci, vp, vp]),
     "exl2_attn_decode_fused_dual": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci,
                                     vp, cll, vp, ci, vp, vp, vp]),
+    "exl2_attn_decode_fused_norm": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci,
+                                         vp, cll, vp, ci, vp, vp, vp, cf, ci, vp]),
     "exl2_paged_attn_q4": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, vp, cll, vp, vp]),
     "exl2_paged_attn_q4_merged": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, vp, cll, vp, vp, ci, vp]),
     "exl2_attn_q4_decode_fused": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, vp, cll, vp, ci, vp, vp]),
@@ -95,6 +100,8 @@ PROTOTYPES = {
     "exl2_q_mlp_chain_info": (ci, [vp, C.POINTER(ci), C.POINTER(vp), C.POINTER(vp)]),
     "exl2_q_matrix_perm_info": (ci, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "exl2_q_attn_forward_1_chain": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, vp]),
+    "exl2_q_attn_forward_1_chain_ex": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, ci, vp]),
+    "exl2_q_attn_head_norm_info": (ci, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(cf), C.POINTER(ci)]),
     "exl2_q_attn_forward_1_chain_rope": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]),
     "exl2_q_attn_forward_2_chain": (ci, [vp, vp, vp, ci, vp, vp, vp, vp, C.POINTER(ci), vp]),
     "exl2_q_mlp_forward_chain": (ci, [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, C.POINTER(ci), vp]),

@@ -28,6 +28,10 @@ class ExLlamaV2Attention:
         self.q4_two_launches = os.environ.get("EXL2_Q4_LAUNCHES", "1") != "4"
         # ... or ONE (RoPE + pack + attention + merge: csrc/attn_q4.hip, the FUSED form; head_dim 128) -- EXL2_Q4_LAUNCHES=2 keeps two
         self.q4_one_launch = os.environ.get("EXL2_Q4_LAUNCHES", "1") == "1"
+        # q / k head norm (cfg.use_qk_norm) in the chained step on an FP16 cache: folded into the one-launch attention (csrc/attn_fused_body.h,
+        # NORM) -- EXL2_QK_NORM_FUSED=0: a launch of its own behind the projections (csrc/head_norm.hip), the form every other route uses
+        self.qk_norm_fused = os.environ.get("EXL2_QK_NORM_FUSED", "1") != "0"
+        self.q_norm = self.k_norm = None
 
     def _q_entries(self, wbits: int):
         """(one-launch step, RoPE + pack, attention from the codes) of a quantized cache: the Q4 mirrors, or the width-carrying ones
@@ -43,13 +47,32 @@ class ExLlamaV2Attention:
         for lin in (self.q_proj, self.k_proj, self.v_proj, self.o_proj):
             lin.load(ck[lin.key])
         self.pre_layernorm = ck[self.key + ".input_layernorm"]
+        if getattr(cfg, "use_qk_norm", False):                                  # attn.py:196-198, 285-289
+            self.q_norm = self._head_norm_weight(ck[self.key + ".self_attn.q_norm"], cfg.num_attention_heads, "q")
+            self.k_norm = self._head_norm_weight(ck[self.key + ".self_attn.k_norm"], cfg.num_key_value_heads, "k")
+        qn = none_tensor if self.q_norm is None else self.q_norm
+        kn = none_tensor if self.k_norm is None else self.k_norm
         self.q_handle = self.ext.make_q_attn(                                   # attn.py:300-330
-            self.pre_layernorm, none_tensor, True, False, cfg.norm_eps,
+            self.pre_layernorm, none_tensor, True, bool(getattr(cfg, "headnorm_rms", True)), cfg.norm_eps,
             self.q_proj.q_handle, self.k_proj.q_handle, self.v_proj.q_handle, self.o_proj.q_handle,
             m.temp_state, none_tensor, m.max_rows, cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads,
-            cfg.head_dim, cfg.max_seq_len, True, cfg.rope_style, cfg.head_dim, none_tensor, none_tensor, none_tensor,
+            cfg.head_dim, cfg.max_seq_len, True, cfg.rope_style, cfg.head_dim, qn, kn, none_tensor,
             none_tensor, False, False)
         return self
+
+    def _head_norm_weight(self, w: torch.Tensor, heads: int, kind: str) -> torch.Tensor:
+        """[heads, head_dim] fp16 on the module's device (a [head_dim] weight is shared by the heads: headnorm.py:59-66);
+        kind "q" | "k": which head range a tensor-parallel rank cuts out (tensor_p.TPAttention)"""
+        hd = self.model.config.head_dim
+        if w.dim() == 1:
+            w = w.view(1, hd).expand(heads, hd)
+        if tuple(w.shape) != (heads, hd):
+            raise RuntimeError(f"{self.key}: head-norm weight of shape {tuple(w.shape)}, expected ({heads}, {hd})")
+        return w.to(device=self.model.device, dtype=torch.float16).contiguous()
+
+    def chain_skip_head_norm(self, cache) -> bool:
+        """chained step on an FP16 cache: q / k leave the projections un-normalised, attend_chain's launch normalises them"""
+        return self.q_norm is not None and self.qk_norm_fused and not getattr(cache, "wbits", 0)
 
     def unload(self):
         if self.q_handle is not None:
@@ -153,14 +176,17 @@ class ExLlamaV2Attention:
                 and cfg.num_attention_heads // cfg.num_key_value_heads <= 64 and cfg.head_dim in (64, 128, 256)
                 and (cfg.num_key_value_heads * cfg.head_dim) % 512 == 0)
 
-    def attend_chain(self, q, k, v, cache, cache_seqlens, block_table, out_invperm):
+    def attend_chain(self, q, k, v, cache, cache_seqlens, block_table, out_invperm, head_norm_pending: bool = False):
         """Decode attention of the chained step (model.GreedyGraphDecoder), output written in o_proj's packed order.  Paged
         FP16 cache: the one-launch kernel.  Paged Q4 / Q6 / Q8 cache: RoPE + pack of the new rows (csrc/cache_q.hip: rope_quant_q4_kernel),
         attention straight from the codes with the split merge inside (csrc/attn_q4.hip) -- the two launches of _attend's q4_direct route.  Raises when
-        the shape needs another path (the decoder then un-chains)."""
+        the shape needs another path (the decoder then un-chains).  head_norm_pending: q / k come un-normalised (q_attn_forward_1_chain
+        with skip_head_norm) -- the FP16 cache's launch normalises them in registers (csrc/attn_fused_body.h, NORM)."""
         cfg, m, ext = self.model.config, self.model, self.ext
         b, q_len = q.shape[0], q.shape[1]
         if getattr(cache, "wbits", 0):
+            if head_norm_pending:
+                raise RuntimeError("attend_chain: a quantized cache's attention takes normalised q / k")
             if not self.q4_chain_capable(cache):
                 raise RuntimeError("attend_chain: shape not covered by the Q4 attention kernel")
             attn_out = m.temp_attn[:b * q_len].view(b, q_len, cfg.num_attention_heads, cfg.head_dim)
@@ -182,8 +208,9 @@ class ExLlamaV2Attention:
             return attn_out
         kc, vc = cache.paged_view(self.layer_idx)
         attn_out = m.temp_attn[:b * q_len].view(b, q_len, cfg.num_attention_heads, cfg.head_dim)
+        hn = (self.q_norm, self.k_norm, cfg.norm_eps, cfg.headnorm_rms) if head_norm_pending else None
         if not ext.attn_decode_fused(q, k, v, kc, vc, attn_out, m.sin, m.cos, cache_seqlens, block_table, 0, cfg.rope_style,
-                                     m.attn_scratch, m.attn_counters, out_invperm=out_invperm):
+                                     m.attn_scratch, m.attn_counters, out_invperm=out_invperm, head_norm=hn):
             raise RuntimeError("attend_chain: shape not covered by the one-launch attention kernel")
         return attn_out
 

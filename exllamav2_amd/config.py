@@ -22,6 +22,8 @@ class ExLlamaV2Config:
     arch: str = "llama"
     num_experts: int = 0                    # > 0: Mixtral-style sparse MLP (moe_mlp.py), experts per token below
     num_experts_per_token: int = 2
+    use_qk_norm: bool = False               # per-head norm of q / k between the projections and RoPE (architecture.py:446,459,609)
+    headnorm_rms: bool = True               # its form: RMS (Qwen3, Gemma3, OLMo2) or LayerNorm over the head (Cohere)
 
     @staticmethod
     def llama2_7b(**kw):
@@ -42,6 +44,22 @@ class ExLlamaV2Config:
         return ExLlamaV2Config(hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
                                num_key_value_heads=8, head_dim=128, vocab_size=32000, num_experts=8,
                                num_experts_per_token=2, arch="mixtral", **kw)
+
+    @staticmethod
+    def qwen3_8b(**kw):
+        d = dict(hidden_size=4096, intermediate_size=12288, num_hidden_layers=36, num_attention_heads=32,
+                 num_key_value_heads=8, head_dim=128, vocab_size=151936, norm_eps=1e-6, rotary_embedding_base=1e6,
+                 use_qk_norm=True, arch="qwen3")
+        d.update(kw)
+        return ExLlamaV2Config(**d)
+
+    @staticmethod
+    def qwen3_0_6b(**kw):
+        d = dict(hidden_size=1024, intermediate_size=3072, num_hidden_layers=28, num_attention_heads=16,
+                 num_key_value_heads=8, head_dim=128, vocab_size=151936, norm_eps=1e-6, rotary_embedding_base=1e6,
+                 use_qk_norm=True, arch="qwen3")
+        d.update(kw)
+        return ExLlamaV2Config(**d)
 
     @staticmethod
     def tiny_test(**kw):

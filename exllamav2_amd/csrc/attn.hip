@@ -197,11 +197,11 @@ KERNEL void __launch_bounds__(256) attn_combine_kernel(const AttnArgs a, int hd)
 }
 
 // ---- one-launch decode step: the body lives in attn_fused_body.h (a device function since round 6) ----
-template <int HDIM, int RB, bool DEP = false>
+template <int HDIM, int RB, bool DEP = false, bool NORM = false>
 KERNEL void __launch_bounds__(ATT_WAVES * 64) attn_fused_kernel(const FusedArgs a)
 {
     DYN_SMEM(smem);
-    attn_fused_body<HDIM, RB, DEP>(a, bid_x(), bid_y(), bid_z(), smem);
+    attn_fused_body<HDIM, RB, DEP, NORM>(a, bid_x(), bid_y(), bid_z(), smem);
 }
 
 // ---- RoPE on q / new k + append of new k, v into the (paged) cache at device-side positions ---------------------------
@@ -475,9 +475,13 @@ static int attn_decode_fused_impl(const void* q, const void* k_new, const void* 
                            int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
                            int page_size, int pages_per_seq, int past_const, float softmax_scale,
                            int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
-                           void* counters, int n_counters, const void* out_invperm, void* out_natural, void* stream)
+                           void* counters, int n_counters, const void* out_invperm, void* out_natural, void* stream,
+                           const void* q_norm = nullptr, const void* k_norm = nullptr, float norm_eps = 0.0f, int norm_rms = 1)
 {
     EXL2_REQUIRE(q && k_new && v_new && k_cache && v_cache && out, "attn_decode_fused: null argument");
+    EXL2_REQUIRE(!q_norm == !k_norm, "attn_decode_fused_norm: q_norm and k_norm come together");
+    const bool norm = q_norm != nullptr;
+    EXL2_REQUIRE(!norm || ((((size_t)q_norm) | ((size_t)k_norm)) & 15) == 0, "attn_decode_fused_norm: norm weights must be 16-byte aligned");
     EXL2_REQUIRE(num_kv_heads > 0 && num_heads % num_kv_heads == 0, "attn_decode_fused: heads %d not a multiple of kv heads %d", num_heads, num_kv_heads);
     EXL2_REQUIRE(rope_style == 0 || (sin && cos), "attn_decode_fused: sin/cos tables missing");
     if (batch <= 0 || q_len <= 0) return EXL2_OK;
@@ -547,6 +551,8 @@ static int attn_decode_fused_impl(const void* q, const void* k_new, const void* 
     const int lpk = head_dim / 8, kpw = 64 / lpk;
     const size_t lds = (size_t)ATT_WAVES * kpw * rb * (head_dim + 2) * 4 + 16 + (size_t)ATT_MAX_PAGES * 4;
     const bool overlapped = chain_sync_active();
+    EXL2_REQUIRE(!(norm && overlapped), "attn_decode_fused_norm: not built for the overlapped chain");
+    a.q_norm = (const f16*)q_norm; a.k_norm = (const f16*)k_norm; a.norm_eps = norm_eps; a.norm_rms = norm_rms;
     if (overlapped)
     {
         ChainLaunch cl;
@@ -557,13 +563,16 @@ static int attn_decode_fused_impl(const void* q, const void* k_new, const void* 
         stream = cl.stream;
     }
 #define FUSED_CASE(HDIM_, RB_) do { if (overlapped) LAUNCH((attn_fused_kernel<HDIM_, RB_, true>), grid, dim3(ATT_WAVES * 64), lds, stream, a); \
+                                    else if (norm) LAUNCH((attn_fused_kernel<HDIM_, RB_, false, true>), grid, dim3(ATT_WAVES * 64), lds, stream, a); \
                                     else LAUNCH((attn_fused_kernel<HDIM_, RB_, false>), grid, dim3(ATT_WAVES * 64), lds, stream, a); } while (0)
 #define FUSED_HD(HDIM_) \
     do { static bool attr_done[EXL2_MAX_DEVICES] = {false}; \
          if (exl2_first_on_device(attr_done)) { (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
                            (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
                            (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                           (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } \
+                           (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+                           (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+                           (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM_, 4, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } \
          switch (rb) { case 1: FUSED_CASE(HDIM_, 1); break; case 2: FUSED_CASE(HDIM_, 2); break; \
                        case 4: FUSED_CASE(HDIM_, 4); break; default: FUSED_CASE(HDIM_, 8); break; } } while (0)
     if (head_dim == 64) FUSED_HD(64);
@@ -586,6 +595,24 @@ int exl2_attn_decode_fused(const void* q, const void* k_new, const void* v_new, 
     return attn_decode_fused_impl(q, k_new, v_new, k_cache, v_cache, out, sin, cos, cache_seqlens, block_table, batch, q_len, num_heads,
                                   num_kv_heads, head_dim, page_size, pages_per_seq, past_const, softmax_scale, rope_style, sincos_size,
                                   nsplit, scratch, scratch_bytes, counters, n_counters, out_invperm, nullptr, stream);
+}
+
+// The same launch with the q / k head norm (head_norm.h) folded in: q and the step's k_new are normalised with q_norm [H, hd] /
+// k_norm [KVH, hd] in registers ahead of the rotation; the cache receives the normalised, rotated k.  Equals exl2_head_norm_qk on
+// (q, k_new) followed by exl2_attn_decode_fused bit for bit -- without writing q / k_new.
+int exl2_attn_decode_fused_norm(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* out,
+                                const void* sin, const void* cos, const int* cache_seqlens, const int* block_table,
+                                int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                                int page_size, int pages_per_seq, int past_const, float softmax_scale,
+                                int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
+                                void* counters, int n_counters, const void* out_invperm,
+                                const void* q_norm, const void* k_norm, float norm_epsilon, int norm_rms, void* stream)
+{
+    EXL2_REQUIRE(q_norm && k_norm, "attn_decode_fused_norm: norm weights missing");
+    return attn_decode_fused_impl(q, k_new, v_new, k_cache, v_cache, out, sin, cos, cache_seqlens, block_table, batch, q_len, num_heads,
+                                  num_kv_heads, head_dim, page_size, pages_per_seq, past_const, softmax_scale, rope_style, sincos_size,
+                                  nsplit, scratch, scratch_bytes, counters, n_counters, out_invperm, nullptr, stream,
+                                  q_norm, k_norm, norm_epsilon, norm_rms);
 }
 
 // The same launch with TWO copies of the output: `out` through out_invperm (o_proj's packed order, what exl2_q_attn_forward_2_chain

@@ -7,6 +7,7 @@
 #include "hw.h"
 #include "chain_sync.h"
 #include "attn_merge.h"
+#include "head_norm.h"
 
 #define ATT_WAVES 4
 #define ATT_UNROLL 4
@@ -54,6 +55,8 @@ struct FusedArgs
     // workgroup that writes a group's final output arrives once (sync_total = batch * kv_heads * row_blocks per launch)
     const u32* sync_wait; u32* sync_signal; u32 sync_total;
     u32* sync_arrive;                                   // every workgroup of the grid reports here on entry (the next launch's gate)
+    // NORM instantiations only (exl2_attn_decode_fused_norm): q / k head norm ahead of the rotation -- weights [H | KVH, hd]
+    const f16* q_norm; const f16* k_norm; float norm_eps; int norm_rms;
 };
 
 // where feature d of query row qrow = (token row) * H + head goes
@@ -113,8 +116,11 @@ template <int LPK> DEV f16x8 rope_neox_frag(f16x8 x, const f16* sin, const f16* 
 // DEP: a launch of the overlapped chain (chain_sync.h; experimental) -- a TEMPLATE parameter since round 5, like the lean kernel's: as
 // run-time tests the polling loop and the agent-scope alternatives of every level-1 load sat in the ordinary launch's code, and the
 // compiler drained the first request (`vmcnt(0)`) in front of them: one round trip at the head of every launch.
+// NORM: the q rows and the step's new k rows are normalised per head (head_norm.h: Qwen3-style q / k norm) in registers, just ahead of
+// the rotation -- the launch then equals exl2_head_norm_qk followed by the plain launch bit for bit, with q / k_new left as they
+// were.  A template parameter for the same reason as DEP: the plain instantiations keep their code.
 // kh / split / zidx = what blockIdx.x / .y / .z are for the kernel; NT = threads taking part (ATT_WAVES * 64); smem: dynamic LDS.
-template <int HDIM, int RB, bool DEP = false>
+template <int HDIM, int RB, bool DEP = false, bool NORM = false>
 DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, const int zidx, u8* const smem)
 {
     constexpr int NT = ATT_WAVES * 64;
@@ -164,6 +170,7 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
     }
     f16x8 qf[RB];
     int limit[RB];
+    f16x8 wq[NORM ? RB : 1], wk;                                // (NORM) the norm weights of the rows' heads: level-1 requests like the rows
     #pragma unroll
     for (int r = 0; r < RB; r++)
     {
@@ -171,8 +178,10 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
         const int j = rr / G, g = rr - j * G;
         const f16* qp = a.q + (((size_t)b * a.s + j) * a.H + kh * G + g) * HDIM + dl * 8;
         qf[r] = dep ? load_agent_f16x8(qp) : *(const f16x8*)qp;
+        if constexpr (NORM) wq[r] = *(const f16x8*)(a.q_norm + (size_t)(kh * G + g) * HDIM + dl * 8);
         limit[r] = j + 1;
     }
+    if constexpr (NORM) wk = *(const f16x8*)(a.k_norm + (size_t)kh * HDIM + dl * 8);
     const int j0 = wv * KPW + group;                            // the new key this stream takes first
     const int jn = j0 < a.s ? j0 : a.s - 1;
     const size_t src0 = (((size_t)b * a.s + jn) * a.KVH + kh) * HDIM + dl * 8;
@@ -260,6 +269,12 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
     const bool any_old = base_first < k_old_end;
     if (any_old) { request_half(kfa, vfa, base_first); request_half(kfb, vfb, base_first + HB * STEP); }
     const bool pre_new = k_start <= past;                       // the stream's first new key is row j0 of this step
+    if constexpr (NORM)
+    {
+        #pragma unroll
+        for (int r = 0; r < RB; r++) qf[r] = head_norm_frag<LPK>(qf[r], wq[r], a.norm_eps, 1.0f / (float)HDIM, a.norm_rms != 0, true);
+        kn0 = head_norm_frag<LPK>(kn0, wk, a.norm_eps, 1.0f / (float)HDIM, a.norm_rms != 0, true);
+    }
     if (a.rope)
     {
         f16x8 cs_q[RB], sn_q[RB], cs_k, sn_k;
@@ -338,6 +353,7 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
             const size_t src = (((size_t)b * a.s + (kp - past)) * a.KVH + kh) * HDIM + dl * 8;
             kfn = dep ? load_agent_f16x8(a.k_new + src) : *(const f16x8*)(a.k_new + src);
             vfn = dep ? load_agent_f16x8(a.v_new + src) : *(const f16x8*)(a.v_new + src);
+            if constexpr (NORM) kfn = head_norm_frag<LPK>(kfn, wk, a.norm_eps, 1.0f / (float)HDIM, a.norm_rms != 0, true);
             if (a.rope) kfn = rope_neox_frag<LPK>(kfn, a.sin, a.cos, kp, dl);
         }
         if (in_range && rblk == 0 && a.k_cache)

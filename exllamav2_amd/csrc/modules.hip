@@ -33,6 +33,11 @@ int exl2_rms_norm(const void* x, const void* w, void* y, float epsilon, int rows
 int exl2_rope_qk(void* x_q, void* x_k, const void* sin, const void* cos, int batch_size,
                  int rows_per_batch_q, int rows_per_batch_k, int head_dim, int num_heads_q, int num_heads_k,
                  int past_len, const int* past_lens, int neox_style, int sincos_size, void* stream);
+int exl2_head_norm_qk(void* q, void* k, const void* q_norm, const void* k_norm, float epsilon, int rms, int batch_size,
+                      int rows_per_batch_q, int rows_per_batch_k, int head_dim, int num_heads_q, int num_heads_k, void* stream);
+int exl2_head_norm_rope_qk(void* q, void* k, const void* q_norm, const void* k_norm, float epsilon, int rms,
+                           const void* sin, const void* cos, int batch_size, int rows_per_batch_q, int rows_per_batch_k, int head_dim,
+                           int num_heads_q, int num_heads_k, int past_len, const int* past_lens, int neox_style, int sincos_size, void* stream);
 int exl2_act_mul(void* x, const void* y, int rows, int width, int act_gelu,
                  const void* r_weights, int r_weights_stride, void* stream);
 int exl2_moe_route(const void* x, const void* gate, void* logits, int rows, int hidden, int num_experts, int topk, void* stream);
@@ -678,7 +683,10 @@ int exl2_make_q_attn(void** handle, const void* layernorm, const void* layernorm
 {
     EXL2_REQUIRE(handle && q_q_proj && q_k_proj && q_v_proj && q_o_proj, "make_q_attn: null projection handle");
     EXL2_REQUIRE(!layernorm || layernorm_is_rms, "make_q_attn: only RMSNorm pre-norm is built (LayerNorm archs out of scope)");
-    EXL2_REQUIRE(!q_norm && !k_norm, "make_q_attn: q/k head norms are not built (non-Llama archs out of scope)");
+    // q / k head norm (Qwen3, Gemma3, OLMo2, Cohere: attn.py:196-198): weights [num_heads | num_kv_heads, head_dim], applied between
+    // the projections and RoPE (q_attn.cu:285-289) by every forward_1 below
+    EXL2_REQUIRE(!q_norm == !k_norm, "make_q_attn: q_norm and k_norm come together");
+    EXL2_REQUIRE(!q_norm || (head_dim % 8 == 0 && head_dim > 0 && head_dim <= 256), "make_q_attn: head norm needs head_dim %% 8 == 0 and <= 256 (got %d)", head_dim);
     EXL2_REQUIRE(!residual_fp32, "make_q_attn: fp32 residual stream is not built");
     // (temp_state may be absent: the reference's tensor-parallel loader makes the handle without scratch, attn.py:259-272,
     // and never runs a forward on it; the forwards below refuse such a handle)
@@ -690,7 +698,7 @@ int exl2_make_q_attn(void** handle, const void* layernorm, const void* layernorm
     a->temp_state = (f16*)temp_state; a->temp_dq = (f16*)temp_dq;
     a->max_rows = max_rows; a->hidden_size = hidden_size; a->num_heads = num_heads; a->num_kv_heads = num_kv_heads;
     a->head_dim = head_dim; a->max_seq_len = max_seq_len; a->has_residual = has_residual; a->rope_style = rope_style;
-    a->sincos_size = sincos_size;
+    a->sincos_size = sincos_size; a->q_norm = (const f16*)q_norm; a->k_norm = (const f16*)k_norm;
     a->post_layernorm = (const f16*)post_layernorm; a->post_layernorm_bias = (const f16*)post_layernorm_bias;
     a->residual_fp32 = residual_fp32; a->use_graphs = use_graphs;
     if (!(a->q_proj->height == hidden_size && a->k_proj->height == hidden_size && a->v_proj->height == hidden_size))
@@ -720,6 +728,23 @@ int exl2_free_q_attn(void* handle)
     return EXL2_OK;
 }
 
+// the head norm of a handle that has one, on the projected q / k rows in place: one launch, with the rotation when the caller asked for
+// it (the reference: head_norm x 2, then rope -- q_attn.cu:285-310)
+static int q_attn_head_norm(QAttn* a, int batch_size, int q_len, int past_len, const int* past_lens, void* temp_q, void* temp_k,
+                            const void* sin, const void* cos, int apply_rope, void* stream, const char* what)
+{
+    EXL2_REQUIRE(!chain_sync_active(), "%s: the q / k head norm is not built for the overlapped chain", what);
+    if (apply_rope && a->rope_style != 0)
+    {
+        EXL2_REQUIRE(sin && cos, "%s: sin/cos tables missing", what);
+        return exl2_head_norm_rope_qk(temp_q, temp_k, a->q_norm, a->k_norm, a->norm_epsilon, a->headnorm_is_rms ? 1 : 0, sin, cos, batch_size,
+                                      q_len * a->num_heads, q_len * a->num_kv_heads, a->head_dim, a->num_heads, a->num_kv_heads,
+                                      past_len, past_lens, a->rope_style == 2, a->sincos_size, stream);
+    }
+    return exl2_head_norm_qk(temp_q, temp_k, a->q_norm, a->k_norm, a->norm_epsilon, a->headnorm_is_rms ? 1 : 0, batch_size,
+                             q_len * a->num_heads, q_len * a->num_kv_heads, a->head_dim, a->num_heads, a->num_kv_heads, stream);
+}
+
 // q_attn_forward_1 (ext_qattn.cpp:115-159 -> q_attn.cu:247-317): q,k,v = proj(rmsnorm(x)); RoPE(q, k) in place.
 // apply_rope = 0 skips the rotation (the caller fuses it with the KV append, exl2_rope_kv_append).
 int exl2_q_attn_forward_1(void* handle, const void* x, int batch_size, int q_len, int past_len, const int* past_lens,
@@ -745,6 +770,7 @@ int exl2_q_attn_forward_1(void* handle, const void* x, int batch_size, int q_len
     for (int i = 0; i < 3; i++) { jobs[i].norm_w = a->layernorm; jobs[i].norm_eps = a->norm_epsilon; }
     jobs[1].rows_as_prev = jobs[2].rows_as_prev = a->qkv_same_perm ? 1 : 0;
     LAUNCH_JOBS(jobs, 3, rows, gptq, stream, "q_attn_forward_1");
+    if (a->q_norm) return q_attn_head_norm(a, batch_size, q_len, past_len, past_lens, temp_q, temp_k, sin, cos, apply_rope, stream, "q_attn_forward_1");
     if (apply_rope && a->rope_style != 0)
     {
         EXL2_REQUIRE(sin && cos, "q_attn_forward_1: sin/cos tables missing");
@@ -924,8 +950,8 @@ int exl2_q_matrix_perm_info(void* q_matrix, const void** perm, const void** invp
     return EXL2_OK;
 }
 
-int exl2_q_attn_forward_1_chain(void* handle, const void* xp, const float* ss, int npart, int rows,
-                                void* temp_q, void* temp_k, void* temp_v, void* stream)
+static int q_attn_forward_1_chain_proj(void* handle, const void* xp, const float* ss, int npart, int rows,
+                                       void* temp_q, void* temp_k, void* temp_v, void* stream)
 {
     EXL2_REQUIRE(handle && xp && ss && temp_q && temp_k && temp_v, "q_attn_forward_1_chain: null argument");
     QAttn* a = (QAttn*)handle;
@@ -943,6 +969,33 @@ int exl2_q_attn_forward_1_chain(void* handle, const void* xp, const float* ss, i
     return EXL2_OK;
 }
 
+// skip_head_norm: the caller's attention launch normalises (exl2_attn_decode_fused_norm) -- q / k leave un-normalised
+int exl2_q_attn_forward_1_chain_ex(void* handle, const void* xp, const float* ss, int npart, int rows,
+                                   void* temp_q, void* temp_k, void* temp_v, int skip_head_norm, void* stream)
+{
+    const int rc = q_attn_forward_1_chain_proj(handle, xp, ss, npart, rows, temp_q, temp_k, temp_v, stream);
+    QAttn* a = (QAttn*)handle;
+    if (rc != EXL2_OK || rows <= 0 || !a->q_norm || skip_head_norm) return rc;
+    return q_attn_head_norm(a, rows, 1, 0, nullptr, temp_q, temp_k, nullptr, nullptr, 0, stream, "q_attn_forward_1_chain");
+}
+
+int exl2_q_attn_forward_1_chain(void* handle, const void* xp, const float* ss, int npart, int rows,
+                                void* temp_q, void* temp_k, void* temp_v, void* stream)
+{
+    return exl2_q_attn_forward_1_chain_ex(handle, xp, ss, npart, rows, temp_q, temp_k, temp_v, 0, stream);
+}
+
+int exl2_q_attn_head_norm_info(void* handle, const void** q_norm, const void** k_norm, float* epsilon, int* rms)
+{
+    EXL2_REQUIRE(handle, "q_attn_head_norm_info: null handle");
+    QAttn* a = (QAttn*)handle;
+    if (q_norm) *q_norm = a->q_norm;
+    if (k_norm) *k_norm = a->k_norm;
+    if (epsilon) *epsilon = a->norm_epsilon;
+    if (rms) *rms = a->headnorm_is_rms ? 1 : 0;
+    return EXL2_OK;
+}
+
 // q_attn_forward_1's full contract (ext_qattn.cpp:115-159: projections of the normalised rows, then RoPE on q and k in place) from a
 // published hand-off: what the module chain behind the operator boundary (dropin/_exl2_fast.cpp) calls -- the reference host reads the
 // rotated q / k (k straight in its cache rows, attn.py:1088-1091), so the rotation cannot be left to the attention launch here.
@@ -952,8 +1005,10 @@ int exl2_q_attn_forward_1_chain_rope(void* handle, const void* xp, const float* 
 {
     EXL2_REQUIRE(handle, "q_attn_forward_1_chain_rope: null handle");
     QAttn* a = (QAttn*)handle;
-    const int rc = exl2_q_attn_forward_1_chain(handle, xp, ss, npart, batch_size * q_len, temp_q, temp_k, temp_v, stream);
-    if (rc != EXL2_OK || batch_size * q_len <= 0 || a->rope_style == 0) return rc;
+    const int rc = q_attn_forward_1_chain_proj(handle, xp, ss, npart, batch_size * q_len, temp_q, temp_k, temp_v, stream);
+    if (rc != EXL2_OK || batch_size * q_len <= 0) return rc;
+    if (a->q_norm) return q_attn_head_norm(a, batch_size, q_len, past_len, past_lens, temp_q, temp_k, sin, cos, 1, stream, "q_attn_forward_1_chain_rope");
+    if (a->rope_style == 0) return rc;
     EXL2_REQUIRE(sin && cos, "q_attn_forward_1_chain_rope: sin/cos tables missing");
     return exl2_rope_qk(temp_q, temp_k, sin, cos, batch_size, q_len * a->num_heads, q_len * a->num_kv_heads,
                         a->head_dim, a->num_heads, a->num_kv_heads, past_len, past_lens, a->rope_style == 2,

@@ -180,6 +180,46 @@ class ExtC:
         """ext_norm.cpp:58-85 (in place)."""
         self.rms_norm(x, w, x, epsilon)
 
+    def head_norm(self, x, w, b, y, epsilon: float, rms: bool) -> None:
+        """ext_norm.cpp:159-200: y = headnorm(x) * w (+ b); x, y half [..., heads, head_dim], w (b) half [heads, head_dim];
+        `none_tensor` for b = no bias."""
+        for t, n in ((x, "x"), (w, "w"), (y, "y")):
+            if t.dtype != torch.float16: raise RuntimeError(f"head_norm: {n} must be half")
+        if not _is_none(b) and b.dtype != torch.float16: raise RuntimeError("head_norm: b must be half")
+        if x.dim() < 2 or w.dim() < 2 or x.shape[-1] != w.shape[-1] or x.shape[-2] != w.shape[-2]:
+            raise RuntimeError("head_norm: x and w have incompatible shapes")
+        if y.dim() < 2 or x.shape[0] != y.shape[0] or x.shape[1] != y.shape[1] or x.numel() != y.numel():
+            raise RuntimeError("head_norm: x and y have incompatible shapes")
+        if not _is_none(b) and (b.dim() < 2 or b.shape[0] != w.shape[0] or b.shape[1] != w.shape[1]):
+            raise RuntimeError("head_norm: b and w have incompatible shapes")
+        head_dim, num_heads = x.shape[-1], x.shape[-2]
+        rows = x.numel() // head_dim // num_heads
+        self.lib.check(self.lib.exl2_head_norm(self._ptr(x, torch.float16, "x"), self._ptr(w, torch.float16, "w"), self._ptr(b),
+                                               self._ptr(y, torch.float16, "y"), float(epsilon), int(bool(rms)), rows, num_heads,
+                                               head_dim, self._stream(x)))
+
+    def head_norm_(self, x, w, b, epsilon: float, rms: bool) -> None:
+        """ext_norm.cpp:202-212 (in place)."""
+        self.head_norm(x, w, b, x, epsilon, rms)
+
+    def head_norm_qk(self, q, k, q_norm, k_norm, epsilon: float, rms: bool, sin=None, cos=None, past_len: int = 0, offsets=None,
+                     neox_style: bool = True) -> None:
+        """q [b, s, heads, hd] and k [b, s, kv_heads, hd] normalised in place in ONE launch (csrc/head_norm.hip); with sin / cos also
+        rotated in that launch -- head_norm_ on each, then rope_ on each, bit for bit."""
+        b, s, nh, hd = q.shape
+        kvh = k.shape[2]
+        if tuple(q_norm.shape) != (nh, hd) or tuple(k_norm.shape) != (kvh, hd) or k.shape[0] != b or k.shape[1] != s or k.shape[3] != hd:
+            raise RuntimeError("head_norm_qk: incompatible shapes")
+        args = (self._ptr(q, torch.float16, "q"), self._ptr(k, torch.float16, "k"), self._ptr(q_norm, torch.float16, "q_norm"),
+                self._ptr(k_norm, torch.float16, "k_norm"), float(epsilon), int(bool(rms)))
+        if _is_none(sin):
+            self.lib.check(self.lib.exl2_head_norm_qk(*args, b, s * nh, s * kvh, hd, nh, kvh, self._stream(q)))
+            return
+        if not _is_none(offsets) and offsets.dtype != torch.int32: raise RuntimeError("head_norm_qk: offsets must be int32")
+        self.lib.check(self.lib.exl2_head_norm_rope_qk(*args, self._ptr(sin, torch.float16, "sin"), self._ptr(cos, torch.float16, "cos"),
+                                                       b, s * nh, s * kvh, hd, nh, kvh, int(past_len), self._ptr(offsets),
+                                                       int(bool(neox_style)), cos.shape[-1], self._stream(q)))
+
     def rope_(self, x, sin, cos, past_len: int, num_heads: int, head_dim: int, offsets, neox_style: bool) -> None:
         """ext_rope.cpp:21-62: in-place rotary embedding on x [batch, ..., head_dim]."""
         for t, n in ((x, "x"), (sin, "sin"), (cos, "cos")):
@@ -561,16 +601,18 @@ class ExtC:
 
     def attn_decode_fused(self, q, k_new, v_new, k_cache, v_cache, out, sin, cos, cache_seqlens, block_table,
                           past_const: int, rope_style: int, scratch, counters, softmax_scale: float | None = None,
-                          sincos_size: int = 0, nsplit: int = 0, out_invperm: int | None = None) -> bool:
+                          sincos_size: int = 0, nsplit: int = 0, out_invperm: int | None = None, head_norm=None) -> bool:
         """One launch for RoPE + append + attention + merge; False when the shape needs the three-launch path.
-        out_invperm (device pointer, u16 [H * hd]): write the output in o_proj's packed order (chained decode)."""
+        out_invperm (device pointer, u16 [H * hd]): write the output in o_proj's packed order (chained decode).
+        head_norm = (q_norm, k_norm, eps, rms) -- fp16 tensors or raw device pointers: the q / k head norm folded into the launch
+        (exl2_attn_decode_fused_norm); q / k_new stay un-normalised."""
         b, s, nh, hd = q.shape
         kvh = k_new.shape[2]
         page_size = k_cache.shape[1]
         pps = 0 if _is_none(block_table) else block_table.shape[1]
         scale = hd ** -0.5 if softmax_scale is None else softmax_scale
         sb = 0 if scratch is None else scratch.numel() * scratch.element_size()
-        rc = self.lib.check(self.lib.exl2_attn_decode_fused(
+        args = (
             self._ptr(q, torch.float16, "q"), self._ptr(k_new, torch.float16, "k_new"),
             self._ptr(v_new, torch.float16, "v_new"), self._ptr(k_cache, torch.float16, "k_cache"),
             self._ptr(v_cache, torch.float16, "v_cache"), self._ptr(out, torch.float16, "out"), self._ptr(sin),
@@ -578,8 +620,14 @@ class ExtC:
             self._ptr(block_table, torch.int32, "block_table"), b, s, nh, kvh, hd, page_size, pps, int(past_const),
             float(scale), int(rope_style), int(sincos_size), int(nsplit), self._ptr(scratch), sb,
             self._ptr(counters, torch.int32, "counters"), 0 if counters is None else counters.numel(),
-            out_invperm or None, self._stream(q)))
-        return rc == 0
+            out_invperm or None)
+        if head_norm is None:
+            return self.lib.check(self.lib.exl2_attn_decode_fused(*args, self._stream(q))) == 0
+        qn, kn, eps, rms = head_norm
+        if not isinstance(qn, int):
+            if tuple(qn.shape) != (nh, hd) or tuple(kn.shape) != (kvh, hd): raise RuntimeError("attn_decode_fused: head-norm weight shapes")
+            qn, kn = self._ptr(qn, torch.float16, "q_norm"), self._ptr(kn, torch.float16, "k_norm")
+        return self.lib.check(self.lib.exl2_attn_decode_fused_norm(*args, qn, kn, float(eps), int(bool(rms)), self._stream(q))) == 0
 
     def flash_attn_with_kvcache(self, q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None,
                                 causal: bool = True, softmax_scale: float | None = None, scratch=None,
@@ -705,11 +753,27 @@ class ExtC:
         self.lib.check(self.lib.exl2_q_matrix_perm_info(q_handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def q_attn_forward_1_chain(self, q_attn, xp, ss, npart: int, rows: int, q_temp, k_temp, v_temp) -> None:
-        self.lib.check(self.lib.exl2_q_attn_forward_1_chain(
+    def q_attn_forward_1_chain(self, q_attn, xp, ss, npart: int, rows: int, q_temp, k_temp, v_temp, skip_head_norm: bool = False) -> None:
+        """skip_head_norm: a handle's q / k head norm is left to the attention launch (attn_decode_fused(head_norm=...))"""
+        self.lib.check(self.lib.exl2_q_attn_forward_1_chain_ex(
             q_attn, self._ptr(xp, torch.float16, "xp"), self._ptr(ss, torch.float32, "ss"), int(npart), int(rows),
             self._ptr(q_temp, torch.float16, "q_temp"), self._ptr(k_temp, torch.float16, "k_temp"),
-            self._ptr(v_temp, torch.float16, "v_temp"), self._stream(xp)))
+            self._ptr(v_temp, torch.float16, "v_temp"), int(bool(skip_head_norm)), self._stream(xp)))
+
+    def q_attn_forward_1_chain_rope(self, q_attn, xp, ss, npart: int, batch_size: int, q_len: int, past_len: int, past_lens,
+                                    q_temp, k_temp, v_temp, sin, cos) -> None:
+        """q_attn_forward_1's contract (projections, head norm, RoPE in place) from a published hand-off"""
+        self.lib.check(self.lib.exl2_q_attn_forward_1_chain_rope(
+            q_attn, self._ptr(xp, torch.float16, "xp"), self._ptr(ss, torch.float32, "ss"), int(npart), int(batch_size), int(q_len),
+            int(past_len), self._ptr(past_lens, torch.int32, "past_lens"), self._ptr(q_temp, torch.float16, "q_temp"),
+            self._ptr(k_temp, torch.float16, "k_temp"), self._ptr(v_temp, torch.float16, "v_temp"), self._ptr(sin), self._ptr(cos),
+            self._stream(xp)))
+
+    def q_attn_head_norm_info(self, q_attn: int):
+        """(q_norm pointer or None, k_norm pointer or None, epsilon, rms) of a q_attn handle"""
+        a, b, e, r = C.c_void_p(), C.c_void_p(), C.c_float(0.0), C.c_int(0)
+        self.lib.check(self.lib.exl2_q_attn_head_norm_info(q_attn, C.byref(a), C.byref(b), C.byref(e), C.byref(r)))
+        return a.value, b.value, float(e.value), bool(r.value)
 
     def q_attn_forward_2_chain(self, q_attn, x, attn_out_packed, rows: int, next_invperm, next_norm_w, xp_out, ss_out) -> int:
         """x += attn_out . Wo; publishes xp_out = x * next_norm_w in the next consumer's order + partial sums of x^2.

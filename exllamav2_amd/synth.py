@@ -223,6 +223,12 @@ def synth_checkpoint(cfg, device, recipe: str = "4.0bpw", seed: int = 0, act_ord
             ck[f"{p}.mlp.down_proj"] = make(inter, h, rec["down_proj"], device, gen, 0.5 / math.sqrt(inter), down_act_order and act_order)
         ck[f"{p}.input_layernorm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen)).half()
         ck[f"{p}.post_attention_layernorm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen)).half()
+        if getattr(cfg, "use_qk_norm", False):
+            # per-head q / k norm weights, every head its own row.  A generator of their own: the layer's other tensors are the
+            # same draws with and without the norm
+            gen_n = gen_for(500000 + i)
+            ck[f"{p}.self_attn.q_norm"] = (1 + 0.1 * torch.randn(cfg.num_attention_heads, cfg.head_dim, device=device, generator=gen_n)).half()
+            ck[f"{p}.self_attn.k_norm"] = (1 + 0.1 * torch.randn(cfg.num_key_value_heads, cfg.head_dim, device=device, generator=gen_n)).half()
     if with_embed:
         ck["model.embed_tokens"] = torch.randn(cfg.vocab_size, h, device=device, generator=gen_for(0)).half()
     if with_head:

@@ -200,6 +200,15 @@ class TPAttention(ExLlamaV2Attention):
         self.pre_layernorm = None
         self.q_handle = None
         self.fused_decode, self.q4_fused = True, True
+        self.q_norm = self.k_norm = None
+        self.qk_norm_fused = True
+
+    def _head_norm_weight(self, w, heads: int, kind: str):
+        """this rank's rows of a per-head q / k norm weight [all heads, head_dim]: its head range / its KV-head range"""
+        if w.dim() == 2:
+            a, b = self.model.tp.q_split if kind == "q" else self.model.tp.kv_split
+            w = w[a:b]
+        return super()._head_norm_weight(w, heads, kind)
 
     # load() and _project_qkv() are the single-device ones: the fused front half (one launch: RMSNorm + q | k | v)
     # runs on the shards with the LOCAL head counts of model.config; the handle's o_proj slot (the o shard) is only

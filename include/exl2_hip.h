@@ -63,6 +63,20 @@ int exl2_rms_norm(const void* x, const void* w, void* y, float epsilon, int rows
 int exl2_rope_qk(void* x_q, void* x_k, const void* sin, const void* cos, int batch_size,
                  int rows_per_batch_q, int rows_per_batch_k, int head_dim, int num_heads_q, int num_heads_k,
                  int past_len, const int* past_lens, int neox_style, int sincos_size, void* stream);
+/* head_norm / head_norm_ (ext_norm.cpp:159-212 -> head_norm_cuda cuda/head_norm.cu:143-168): x, y fp16 [rows, num_heads, head_dim],
+   w (and the nullable bias b) fp16 [num_heads, head_dim]; rms != 0: y = x * w * rsqrt(mean(x^2) + eps), else LayerNorm over the head;
+   y == x: in place.  head_dim: any multiple of 8 up to 256. */
+int exl2_head_norm(const void* x, const void* w, const void* b, void* y, float epsilon, int rms, int rows, int num_heads,
+                   int head_dim, void* stream);
+/* q [batch, rows_per_batch_q, head_dim] and k [batch, rows_per_batch_k, head_dim] normalised in place with q_norm [num_heads_q, head_dim] /
+   k_norm [num_heads_k, head_dim] in ONE launch (the two head_norm_cuda calls of q_attn.cu:285-289; no bias there) ... */
+int exl2_head_norm_qk(void* q, void* k, const void* q_norm, const void* k_norm, float epsilon, int rms, int batch_size,
+                      int rows_per_batch_q, int rows_per_batch_k, int head_dim, int num_heads_q, int num_heads_k, void* stream);
+/* ... and with rope_cuda_qk behind it in the same launch (q_attn.cu:285-310: three launches); the rotation reads the fp16-rounded
+   normalised values, so the result is exl2_head_norm_qk followed by exl2_rope_qk bit for bit */
+int exl2_head_norm_rope_qk(void* q, void* k, const void* q_norm, const void* k_norm, float epsilon, int rms,
+                           const void* sin, const void* cos, int batch_size, int rows_per_batch_q, int rows_per_batch_k, int head_dim,
+                           int num_heads_q, int num_heads_k, int past_len, const int* past_lens, int neox_style, int sincos_size, void* stream);
 /* act_mul_cuda (cuda/q_mlp.cu:238-258): x = act(x) * y */
 int exl2_act_mul(void* x, const void* y, int rows, int width, int act_gelu,
                  const void* r_weights, int r_weights_stride, void* stream);
@@ -182,6 +196,16 @@ int exl2_attn_decode_fused_dual(const void* q, const void* k_new, const void* v_
                                 int page_size, int pages_per_seq, int past_const, float softmax_scale,
                                 int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
                                 void* counters, int n_counters, const void* out_invperm, void* out_natural, void* stream);
+/* exl2_attn_decode_fused with the q / k head norm folded in (Qwen3-style attention; q_norm [num_heads, head_dim], k_norm
+   [num_kv_heads, head_dim], head_norm.cu numerics): q and k_new are normalised in registers ahead of the rotation, the cache receives
+   the normalised, rotated k.  Equals exl2_head_norm_qk(q, k_new) + exl2_attn_decode_fused bit for bit; q / k_new are not written. */
+int exl2_attn_decode_fused_norm(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* out,
+                                const void* sin, const void* cos, const int* cache_seqlens, const int* block_table,
+                                int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                                int page_size, int pages_per_seq, int past_const, float softmax_scale,
+                                int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
+                                void* counters, int n_counters, const void* out_invperm,
+                                const void* q_norm, const void* k_norm, float norm_epsilon, int norm_rms, void* stream);
 
 /* Decode attention straight from the Q4 KV cache (ExLlamaV2Cache_Q4, cache.py:409-606; format cache_q.cuh:4-185): replaces
    q_to_fp16_kv of the whole live range (cache.py:472-514) + attention over the fp16 temp.  k_new / v_new (nullable, fp16
@@ -254,7 +278,9 @@ int exl2_rope_quant_append_q(void* q, void* k_new, const void* v_new, void* k_co
 
 /* ---- fused modules --------------------------------------------------------------------------------------------------- */
 
-/* make_q_attn (ext_qattn.cpp:24-104), q_attn_forward_1 (:115-159), q_attn_forward_2 (:161-191) */
+/* make_q_attn (ext_qattn.cpp:24-104), q_attn_forward_1 (:115-159), q_attn_forward_2 (:161-191).  q_norm / k_norm (both or neither;
+   fp16 [num_heads | num_kv_heads, head_dim], head_dim % 8 == 0 and <= 256): the per-head norm between the projections and RoPE
+   (q_attn.cu:285-289), in the form headnorm_is_rms selects, eps = norm_epsilon -- applied by every forward_1 entry below. */
 int exl2_make_q_attn(void** handle, const void* layernorm, const void* layernorm_bias, int layernorm_is_rms,
                      int headnorm_is_rms, float norm_epsilon, void* q_q_proj, void* q_k_proj, void* q_v_proj,
                      void* q_o_proj, void* temp_state, void* temp_dq, int max_rows, int hidden_size, int num_heads,
@@ -309,6 +335,12 @@ int exl2_q_matrix_perm_info(void* q_matrix, const void** perm, const void** invp
 /* q, k, v = proj(rmsnorm(x)) from (xp, ss); no RoPE (the attention launch rotates) */
 int exl2_q_attn_forward_1_chain(void* handle, const void* xp, const float* ss, int npart, int rows,
                                 void* temp_q, void* temp_k, void* temp_v, void* stream);
+/* the same with a switch: skip_head_norm != 0 leaves the q / k head norm of a handle that has one to the caller's attention launch
+   (exl2_attn_decode_fused_norm, weights from exl2_q_attn_head_norm_info) */
+int exl2_q_attn_forward_1_chain_ex(void* handle, const void* xp, const float* ss, int npart, int rows,
+                                   void* temp_q, void* temp_k, void* temp_v, int skip_head_norm, void* stream);
+/* the handle's head-norm weights (NULL: none), epsilon and form */
+int exl2_q_attn_head_norm_info(void* handle, const void** q_norm, const void** k_norm, float* epsilon, int* rms);
 /* the same + RoPE(q, k) in place: q_attn_forward_1's whole contract (ext_qattn.cpp:115-159) from a published hand-off */
 int exl2_q_attn_forward_1_chain_rope(void* handle, const void* xp, const float* ss, int npart, int batch_size, int q_len, int past_len,
                                      const int* past_lens, void* temp_q, void* temp_k, void* temp_v, const void* sin, const void* cos,
