@@ -72,6 +72,8 @@ PROTOTYPES = {
                                     vp, cll, vp, ci, vp, vp, vp]),
     "exl2_attn_decode_fused_norm": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci,
                                          vp, cll, vp, ci, vp, vp, vp, cf, ci, vp]),
+    "exl2_attn_decode_fused_step": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci,
+                                         vp, cll, vp, ci, vp, vp, vp, cf, ci, vp, ci, vp]),
     "exl2_paged_attn_q4": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, vp, cll, vp, vp]),
     "exl2_paged_attn_q4_merged": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, vp, cll, vp, vp, ci, vp]),
     "exl2_attn_q4_decode_fused": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, cf, ci, ci, ci, vp, cll, vp, ci, vp, vp]),
@@ -108,6 +110,7 @@ PROTOTYPES = {
     "exl2_q_mlp_forward_chain_part": (ci, [vp, ci, ci, vp, vp, vp, ci, ci, vp, vp, vp, vp, C.POINTER(ci), vp]),
     "exl2_gemm_half_q_half_chain": (ci, [vp, vp, ci, cf, vp, vp, ci, vp]),
     "exl2_embed_rows_chain": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "exl2_embed_rows_chain_step": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
     "exl2_chain_set_tiled": (ci, [ci]),
     "exl2_publish_rows": (ci, [vp, ci, ci, vp, vp, vp, vp, vp]),
     "exl2_gather_f16": (ci, [vp, vp, vp, ci, vp]),

@@ -176,12 +176,14 @@ class ExLlamaV2Attention:
                 and cfg.num_attention_heads // cfg.num_key_value_heads <= 64 and cfg.head_dim in (64, 128, 256)
                 and (cfg.num_key_value_heads * cfg.head_dim) % 512 == 0)
 
-    def attend_chain(self, q, k, v, cache, cache_seqlens, block_table, out_invperm, head_norm_pending: bool = False):
+    def attend_chain(self, q, k, v, cache, cache_seqlens, block_table, out_invperm, head_norm_pending: bool = False,
+                     rope_now=None, identity_table: bool = False):
         """Decode attention of the chained step (model.GreedyGraphDecoder), output written in o_proj's packed order.  Paged
         FP16 cache: the one-launch kernel.  Paged Q4 / Q6 / Q8 cache: RoPE + pack of the new rows (csrc/cache_q.hip: rope_quant_q4_kernel),
         attention straight from the codes with the split merge inside (csrc/attn_q4.hip) -- the two launches of _attend's q4_direct route.  Raises when
         the shape needs another path (the decoder then un-chains).  head_norm_pending: q / k come un-normalised (q_attn_forward_1_chain
-        with skip_head_norm) -- the FP16 cache's launch normalises them in registers (csrc/attn_fused_body.h, NORM)."""
+        with skip_head_norm) -- the FP16 cache's launch normalises them in registers (csrc/attn_fused_body.h, NORM).
+        rope_now / identity_table: handed to the FP16 cache's launch (ext.attn_decode_fused)."""
         cfg, m, ext = self.model.config, self.model, self.ext
         b, q_len = q.shape[0], q.shape[1]
         if getattr(cache, "wbits", 0):
@@ -210,7 +212,8 @@ class ExLlamaV2Attention:
         attn_out = m.temp_attn[:b * q_len].view(b, q_len, cfg.num_attention_heads, cfg.head_dim)
         hn = (self.q_norm, self.k_norm, cfg.norm_eps, cfg.headnorm_rms) if head_norm_pending else None
         if not ext.attn_decode_fused(q, k, v, kc, vc, attn_out, m.sin, m.cos, cache_seqlens, block_table, 0, cfg.rope_style,
-                                     m.attn_scratch, m.attn_counters, out_invperm=out_invperm, head_norm=hn):
+                                     m.attn_scratch, m.attn_counters, out_invperm=out_invperm, head_norm=hn,
+                                     rope_now=rope_now, identity_table=identity_table):
             raise RuntimeError("attend_chain: shape not covered by the one-launch attention kernel")
         return attn_out
 

@@ -197,11 +197,19 @@ KERNEL void __launch_bounds__(256) attn_combine_kernel(const AttnArgs a, int hd)
 }
 
 // ---- one-launch decode step: the body lives in attn_fused_body.h (a device function since round 6) ----
-template <int HDIM, int RB, bool DEP = false, bool NORM = false>
+// FAST (attn_fused_body.h): bit 0 = SPEC_KV -- split 0 (blockIdx.y == 0) runs the instantiation whose first batch of cached rows is a
+// level-1 request, every other split today's; the two never meet again, so neither waits for the other's requests.  bit 1 = ROPE_NOW.
+template <int HDIM, int RB, bool DEP = false, bool NORM = false, int FAST = 0>
 KERNEL void __launch_bounds__(ATT_WAVES * 64) attn_fused_kernel(const FusedArgs a)
 {
     DYN_SMEM(smem);
-    attn_fused_body<HDIM, RB, DEP, NORM>(a, bid_x(), bid_y(), bid_z(), smem);
+    constexpr bool RN = (FAST & 2) != 0;
+    if constexpr ((FAST & 1) != 0)
+    {
+        if (bid_y() == 0) attn_fused_body<HDIM, RB, DEP, NORM, true, RN>(a, bid_x(), 0, bid_z(), smem);
+        else attn_fused_body<HDIM, RB, DEP, NORM, false, RN>(a, bid_x(), bid_y(), bid_z(), smem);
+    }
+    else attn_fused_body<HDIM, RB, DEP, NORM, false, RN>(a, bid_x(), bid_y(), bid_z(), smem);
 }
 
 // ---- RoPE on q / new k + append of new k, v into the (paged) cache at device-side positions ---------------------------
@@ -467,6 +475,38 @@ int exl2_paged_attn_ex(const void* q, const void* k_cache, const void* v_cache, 
     return EXL2_OK;
 }
 
+// EXL2_ATT_SPEC (A/B): which of the two level-1 short cuts of the one-launch decode attention a launch may take -- bit 0: the first batch
+// of cached rows of split 0 (launches without a block table), bit 1: the step's rotary row from rope_now.  Unset = 3 = both, 0 = the
+// request order of round 11.  Read once (per call under EXL2_ENV_DYNAMIC, as the tests flip it in place) and turned into the
+// kernel's instantiation: no run-time test in the launch itself.
+extern "C++" {
+static int att_spec_mode()
+{
+    auto parse = []() { const char* e = getenv("EXL2_ATT_SPEC"); return e ? (atoi(e) & 3) : 3; };
+    static const bool dyn = getenv("EXL2_ENV_DYNAMIC") != nullptr;
+    static const int v = parse();
+    return dyn ? parse() : v;
+}
+
+// a FAST instantiation of the one-launch decode attention, with its LDS allowance on first use
+template <int HDIM, int RB, bool NORM, int FAST>
+static void fused_launch_fast(const FusedArgs& a, dim3 grid, size_t lds, void* stream)
+{
+    static bool attr_done[EXL2_MAX_DEVICES] = {false};
+    if (exl2_first_on_device(attr_done))
+        (void)hipFuncSetAttribute((const void*)attn_fused_kernel<HDIM, RB, false, NORM, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    LAUNCH((attn_fused_kernel<HDIM, RB, false, NORM, FAST>), grid, dim3(ATT_WAVES * 64), lds, stream, a);
+}
+template <int HDIM, int RB>
+static void fused_launch_fast_pick(const FusedArgs& a, bool norm, int fast, dim3 grid, size_t lds, void* stream)
+{
+    if (norm) { if (fast == 1) fused_launch_fast<HDIM, RB, true, 1>(a, grid, lds, stream); else if (fast == 2) fused_launch_fast<HDIM, RB, true, 2>(a, grid, lds, stream);
+                else fused_launch_fast<HDIM, RB, true, 3>(a, grid, lds, stream); }
+    else      { if (fast == 1) fused_launch_fast<HDIM, RB, false, 1>(a, grid, lds, stream); else if (fast == 2) fused_launch_fast<HDIM, RB, false, 2>(a, grid, lds, stream);
+                else fused_launch_fast<HDIM, RB, false, 3>(a, grid, lds, stream); }
+}
+}   // extern "C++"
+
 // One-launch decode-step attention (see attn_fused_kernel).  Returns 1 (nothing launched) when the shape is outside what
 // the fused kernel covers -- the caller then uses exl2_rope_kv_append + exl2_paged_attn.  q / k_new are NOT modified.
 // `counters`: >= batch * kv_heads * row_blocks zeroed u32, left zeroed.  Positions: past = past_const + cache_seqlens[b].
@@ -476,7 +516,8 @@ static int attn_decode_fused_impl(const void* q, const void* k_new, const void* 
                            int page_size, int pages_per_seq, int past_const, float softmax_scale,
                            int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
                            void* counters, int n_counters, const void* out_invperm, void* out_natural, void* stream,
-                           const void* q_norm = nullptr, const void* k_norm = nullptr, float norm_eps = 0.0f, int norm_rms = 1)
+                           const void* q_norm = nullptr, const void* k_norm = nullptr, float norm_eps = 0.0f, int norm_rms = 1,
+                           const void* rope_now = nullptr, int identity_table = 0)
 {
     EXL2_REQUIRE(q && k_new && v_new && k_cache && v_cache && out, "attn_decode_fused: null argument");
     EXL2_REQUIRE(!q_norm == !k_norm, "attn_decode_fused_norm: q_norm and k_norm come together");
@@ -552,6 +593,28 @@ static int attn_decode_fused_impl(const void* q, const void* k_new, const void* 
     const size_t lds = (size_t)ATT_WAVES * kpw * rb * (head_dim + 2) * 4 + 16 + (size_t)ATT_MAX_PAGES * 4;
     const bool overlapped = chain_sync_active();
     EXL2_REQUIRE(!(norm && overlapped), "attn_decode_fused_norm: not built for the overlapped chain");
+    // the level-1 short cuts (attn_fused_body.h: SPEC_KV, ROPE_NOW); everything above -- row blocks, splits, grid -- was decided without them
+    int fast = 0;
+    if (!overlapped)
+    {
+        const int mode = att_spec_mode();
+        // (an identity table -- entry [b][p] = b * pages_per_seq + p, the caller's word -- addresses what the launch without a table
+        // does with pages_per_seq * page_size rows per sequence)
+        const bool no_table = !block_table || (identity_table && pages_per_seq > 0);
+        if ((mode & 1) && no_table && page_size > 0)
+        {
+            if (block_table) { a.block_table = nullptr; a.page_size = page_size * pages_per_seq; }
+            a.kv_row_max = a.page_size - 1;
+            fast |= 1;
+        }
+        if ((mode & 2) && rope_now && q_len == 1 && a.rope)
+        {
+            EXL2_REQUIRE(cache_seqlens && past_const == 0, "attn_decode_fused_step: rope_now holds the rows of position cache_seqlens[b]");
+            EXL2_REQUIRE((((size_t)rope_now) & 15) == 0, "attn_decode_fused_step: rope_now must be 16-byte aligned");
+            a.rope_now = (const f16*)rope_now;
+            fast |= 2;
+        }
+    }
     a.q_norm = (const f16*)q_norm; a.k_norm = (const f16*)k_norm; a.norm_eps = norm_eps; a.norm_rms = norm_rms;
     if (overlapped)
     {
@@ -562,7 +625,8 @@ static int attn_decode_fused_impl(const void* q, const void* k_new, const void* 
         a.sync_arrive = cl.arrive;
         stream = cl.stream;
     }
-#define FUSED_CASE(HDIM_, RB_) do { if (overlapped) LAUNCH((attn_fused_kernel<HDIM_, RB_, true>), grid, dim3(ATT_WAVES * 64), lds, stream, a); \
+#define FUSED_CASE(HDIM_, RB_) do { if (fast) fused_launch_fast_pick<HDIM_, RB_>(a, norm, fast, grid, lds, stream); \
+                                    else if (overlapped) LAUNCH((attn_fused_kernel<HDIM_, RB_, true>), grid, dim3(ATT_WAVES * 64), lds, stream, a); \
                                     else if (norm) LAUNCH((attn_fused_kernel<HDIM_, RB_, false, true>), grid, dim3(ATT_WAVES * 64), lds, stream, a); \
                                     else LAUNCH((attn_fused_kernel<HDIM_, RB_, false>), grid, dim3(ATT_WAVES * 64), lds, stream, a); } while (0)
 #define FUSED_HD(HDIM_) \
@@ -631,6 +695,25 @@ int exl2_attn_decode_fused_dual(const void* q, const void* k_new, const void* v_
                                   cache_seqlens, block_table, batch, q_len, num_heads,
                                   num_kv_heads, head_dim, page_size, pages_per_seq, past_const, softmax_scale, rope_style, sincos_size,
                                   nsplit, scratch, scratch_bytes, counters, n_counters, out_invperm, out_natural, stream);
+}
+
+// The launch as a step of the chained decode makes it (model.GreedyGraphDecoder): q_norm / k_norm nullable (both or neither);
+// rope_now nullable: [batch, 2, head_dim] fp16, the sin and the cos row of position cache_seqlens[b] (exl2_embed_rows_chain_step
+// leaves them there at the head of the step) -- taken at q_len 1 instead of the table rows behind the length; identity_table != 0:
+// the caller's word that block_table[b][p] == b * pages_per_seq + p, i.e. that the cache is contiguous per sequence.
+int exl2_attn_decode_fused_step(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* out,
+                                const void* sin, const void* cos, const int* cache_seqlens, const int* block_table,
+                                int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                                int page_size, int pages_per_seq, int past_const, float softmax_scale,
+                                int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
+                                void* counters, int n_counters, const void* out_invperm,
+                                const void* q_norm, const void* k_norm, float norm_epsilon, int norm_rms,
+                                const void* rope_now, int identity_table, void* stream)
+{
+    return attn_decode_fused_impl(q, k_new, v_new, k_cache, v_cache, out, sin, cos, cache_seqlens, block_table, batch, q_len, num_heads,
+                                  num_kv_heads, head_dim, page_size, pages_per_seq, past_const, softmax_scale, rope_style, sincos_size,
+                                  nsplit, scratch, scratch_bytes, counters, n_counters, out_invperm, nullptr, stream,
+                                  q_norm, k_norm, norm_epsilon, norm_rms, rope_now, identity_table);
 }
 
 // RoPE on q and k_new in place (rope.cu numerics) and, when caches are given, append of the rotated k_new and of v_new at

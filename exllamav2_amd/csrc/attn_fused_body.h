@@ -57,6 +57,10 @@ struct FusedArgs
     u32* sync_arrive;                                   // every workgroup of the grid reports here on entry (the next launch's gate)
     // NORM instantiations only (exl2_attn_decode_fused_norm): q / k head norm ahead of the rotation -- weights [H | KVH, hd]
     const f16* q_norm; const f16* k_norm; float norm_eps; int norm_rms;
+    // ROPE_NOW instantiations only (exl2_attn_decode_fused_step): [b][2][HDIM], the sin and the cos row of each sequence's position in
+    // this step, left there by the step's first launch (elementwise.hip: embed_rows_chain_kernel) -- a level-1 request, not one behind the length
+    const f16* rope_now;
+    int kv_row_max;                                     // SPEC_KV: last row a sequence's cache holds (speculative rows are clamped to it)
 };
 
 // where feature d of query row qrow = (token row) * H + head goes
@@ -75,6 +79,44 @@ DEV int fused_active_splits(const FusedArgs& a, int total)
         if (e2 > eff) eff = e2;
     }
     return eff < 1 ? 1 : (eff > a.nsplit ? a.nsplit : eff);
+}
+
+// merge_split_partials (attn_merge.h) with every multiply-add SPELLED OUT.  The merge is run by whichever split arrives last, and
+// a kernel with SPEC_KV holds two compiled copies of the body -- split 0's and the other splits'.  Left to the compiler, the two
+// copies fused DIFFERENT steps of the unrolled update into FMAs (gfx950 code of <256, 2, NORM, FAST 1>: the third partial unfused
+// in one copy, the fifth in the other), so the last bit of the result depended on the order the splits finished in.  As written
+// here -- w products rounded, then one FMA each -- every copy computes the same; it is the form the compiler gave all but one
+// step of the single copy before.
+DEV float fused_merge_split_partials(const float* part_o, const float* part_ml, size_t qrow, int nsplit, int eff, int hd, int d)
+{
+    #pragma clang fp contract(off)
+    float M = -1.0e30f, L = 0.0f, O = 0.0f;
+    for (int s0 = 0; s0 < eff; s0 += 8)
+    {
+        float mv[8], lv[8], ov[8];
+        #pragma unroll
+        for (int u = 0; u < 8; u++)
+        {
+            const int s2 = s0 + u < eff ? s0 + u : eff - 1;
+            const float* ml = part_ml + (qrow * (size_t)nsplit + s2) * 2;
+            const float* po = part_o + (qrow * (size_t)nsplit + s2) * hd + d;
+            mv[u] = load_agent_f32(ml); lv[u] = load_agent_f32(ml + 1); ov[u] = load_agent_f32(po);
+        }
+        #pragma unroll
+        for (int u = 0; u < 8; u++)
+        {
+            if (s0 + u < eff)
+            {
+                const float m_new = fmaxf(M, mv[u]);
+                const float alpha = fast_exp(M - m_new), w = fast_exp(mv[u] - m_new);
+                const float lw = lv[u] * w, ow = ov[u] * w;
+                L = __builtin_fmaf(L, alpha, lw);
+                O = __builtin_fmaf(O, alpha, ow);
+                M = m_new;
+            }
+        }
+    }
+    return L > 0.0f ? O / L : 0.0f;
 }
 
 template <int HDIM> DEV size_t fused_out_index(const FusedArgs& a, size_t qrow, int d)
@@ -119,8 +161,17 @@ template <int LPK> DEV f16x8 rope_neox_frag(f16x8 x, const f16* sin, const f16* 
 // NORM: the q rows and the step's new k rows are normalised per head (head_norm.h: Qwen3-style q / k norm) in registers, just ahead of
 // the rotation -- the launch then equals exl2_head_norm_qk followed by the plain launch bit for bit, with q / k_new left as they
 // were.  A template parameter for the same reason as DEP: the plain instantiations keep their code.
+// SPEC_KV (split 0 of a launch WITHOUT a block table; the kernel calls this instantiation for blockIdx.y == 0 only): the first batch
+// of cached K / V rows is a level-1 request.  Split 0 starts at key 0 whatever the length is, so the ADDRESSES of that batch need
+// nothing from memory -- only the masking does.  Rows at positions >= past may never have been written (any bit pattern, NaNs
+// included) or are being written by this very launch: a lane beyond the split's cached keys takes ZEROS for K and for V (before,
+// such a lane re-read the split's first row and `p * v` was 0 * finite: zeros give the same bits, a NaN would not).
+// ROPE_NOW (one new token per sequence): the rotary row of q and of the new k comes from a.rope_now at level 1 -- every layer of a
+// step rotates by the same position, the step's first launch looks it up once.  The same table rows, hence the same bits.
+// Template parameters for the same reason as DEP: with either as a run-time alternative the compiler waits where the two request
+// orders meet.
 // kh / split / zidx = what blockIdx.x / .y / .z are for the kernel; NT = threads taking part (ATT_WAVES * 64); smem: dynamic LDS.
-template <int HDIM, int RB, bool DEP = false, bool NORM = false>
+template <int HDIM, int RB, bool DEP = false, bool NORM = false, bool SPEC_KV = false, bool ROPE_NOW = false>
 DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, const int zidx, u8* const smem)
 {
     constexpr int NT = ATT_WAVES * 64;
@@ -157,8 +208,10 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
     // address the compiler made it a scalar load and sank it behind the wait for the vector loads -- a dependent level of its own
     // again; as a volatile load it is waited for on the spot)
     const int p_ld = ld_nt(a.cache_seqlens ? a.cache_seqlens + b : (const int*)a.q);
-    const bool spec = a.block_table != nullptr && split == 0;
-    const int tab_spec = ld_nt(spec ? a.block_table + (size_t)b * a.pages_per_seq : (const int*)a.q);
+    // (SPEC_KV: no block table, hence no page entry to request)
+    const bool spec = !SPEC_KV && a.block_table != nullptr && split == 0;
+    int tab_spec = 0;
+    if constexpr (!SPEC_KV) tab_spec = ld_nt(spec ? a.block_table + (size_t)b * a.pages_per_seq : (const int*)a.q);
     if constexpr (DEP) if (a.sync_wait)
     {
         // overlapped chain: q / k_new / v_new are read behind the wait; workgroups of unused splits leave before it
@@ -187,6 +240,35 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
     const size_t src0 = (((size_t)b * a.s + jn) * a.KVH + kh) * HDIM + dl * 8;
     f16x8 kn0 = dep ? load_agent_f16x8(a.k_new + src0) : *(const f16x8*)(a.k_new + src0);
     const f16x8 vn0 = dep ? load_agent_f16x8(a.v_new + src0) : *(const f16x8*)(a.v_new + src0);
+    const size_t row_stride = (size_t)a.KVH * HDIM;
+    constexpr int STEP = ATT_WAVES * KPW;
+    constexpr int UNR = RB <= 2 ? 2 * ATT_UNROLL : ATT_UNROLL;   // keys of UNR steps requested together (128 = a whole split at 1-2 rows)
+    constexpr int HB = UNR / 2;
+    f16x8 kfa[HB], vfa[HB], kfb[HB], vfb[HB];
+    f16x8 cs_now, sn_now;
+    if constexpr (ROPE_NOW)
+    {
+        const f16* rn = a.rope_now + (size_t)b * (2 * HDIM) + (size_t)(dl % (LPK / 2)) * 8;
+        sn_now = *(const f16x8*)rn;
+        cs_now = *(const f16x8*)(rn + HDIM);
+    }
+    if constexpr (SPEC_KV)
+    {
+        // split 0, no block table: key wv * KPW + u * STEP + group of sequence b sits in row b * page_size + key -- clamped to the
+        // sequence's last row, so every address lies inside the cache tensor whatever the length turns out to be
+        #pragma unroll
+        for (int h = 0; h < 2; h++)
+        {
+            #pragma unroll
+            for (int u = 0; u < HB; u++)
+            {
+                const int kpos = wv * KPW + (h * HB + u) * STEP + group;
+                const size_t off = ((size_t)b * a.page_size + min(kpos, a.kv_row_max)) * row_stride + (size_t)kh * HDIM + dl * 8;
+                if (h == 0) { kfa[u] = ld_nt((const f16x8*)(a.k_cache + off)); vfa[u] = ld_nt((const f16x8*)(a.v_cache + off)); }
+                else        { kfb[u] = ld_nt((const f16x8*)(a.k_cache + off)); vfb[u] = ld_nt((const f16x8*)(a.v_cache + off)); }
+            }
+        }
+    }
     int out_pre = 0;
     if (a.out_invperm && tid() < nrows * HDIM)
     {
@@ -234,18 +316,14 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
         if (a.block_table) return (size_t)pg_lds[(kp >> a.page_shift) - pg0] * a.page_size + (kp & (a.page_size - 1));
         return (size_t)b * a.page_size + kp;
     };
-    const size_t row_stride = (size_t)a.KVH * HDIM;
     const int k_old_end = min(k_end, past);
-    constexpr int STEP = ATT_WAVES * KPW;
-    constexpr int UNR = RB <= 2 ? 2 * ATT_UNROLL : ATT_UNROLL;   // keys of UNR steps requested together (128 = a whole split at 1-2 rows)
 
     // ---- request level 2: what needs the length -- the first batch of cached keys, the rotary rows of the queries and of
-    // the new key -- again together, before anything is used
+    // the new key -- again together, before anything is used.  (SPEC_KV / ROPE_NOW: the batch / the rotary row went out at level 1;
+    // a one-token step of split 0 with both has no level 2 at all)
     // Two half-batches (round 5): while one is used the other is in flight.  EVERY request is unconditional -- a position beyond the
     // split's cached keys reads the split's first row (a cache hit; its score is masked) -- so that the compiler's count of the loads in
     // flight stays exact and the wait in front of a half-batch is `vmcnt(loads of the other half)`, not `vmcnt(0)`.
-    constexpr int HB = UNR / 2;
-    f16x8 kfa[HB], vfa[HB], kfb[HB], vfb[HB];
     const int base_first = k_start + wv * KPW;
     auto request_half = [&](f16x8 (&kf)[HB], f16x8 (&vf)[HB], const int base0)
     {
@@ -267,7 +345,8 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
         }
     };
     const bool any_old = base_first < k_old_end;
-    if (any_old) { request_half(kfa, vfa, base_first); request_half(kfb, vfb, base_first + HB * STEP); }
+    // (SPEC_KV: that batch went out at level 1)
+    if constexpr (!SPEC_KV) if (any_old) { request_half(kfa, vfa, base_first); request_half(kfb, vfb, base_first + HB * STEP); }
     const bool pre_new = k_start <= past;                       // the stream's first new key is row j0 of this step
     if constexpr (NORM)
     {
@@ -275,7 +354,13 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
         for (int r = 0; r < RB; r++) qf[r] = head_norm_frag<LPK>(qf[r], wq[r], a.norm_eps, 1.0f / (float)HDIM, a.norm_rms != 0, true);
         kn0 = head_norm_frag<LPK>(kn0, wk, a.norm_eps, 1.0f / (float)HDIM, a.norm_rms != 0, true);
     }
-    if (a.rope)
+    if constexpr (ROPE_NOW)
+    {
+        #pragma unroll
+        for (int r = 0; r < RB; r++) qf[r] = rope_neox_apply<LPK>(qf[r], cs_now, sn_now, dl);
+        kn0 = rope_neox_apply<LPK>(kn0, cs_now, sn_now, dl);
+    }
+    else if (a.rope)
     {
         f16x8 cs_q[RB], sn_q[RB], cs_k, sn_k;
         #pragma unroll
@@ -326,7 +411,9 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
     for (int u = 0; u < HB; u++) \
     { \
         const int kpos_ = (BASE) + u * STEP + group; \
-        if ((BASE) + u * STEP < k_old_end) attend(KF[u], VF[u], kpos_, kpos_ < k_old_end); \
+        f16x8 kf_ = KF[u], vf_ = VF[u]; \
+        if constexpr (SPEC_KV) if (!(kpos_ < k_old_end)) { kf_ = (f16x8)(f16)0.0f; vf_ = (f16x8)(f16)0.0f; } \
+        if ((BASE) + u * STEP < k_old_end) attend(kf_, vf_, kpos_, kpos_ < k_old_end); \
     }
     for (int base0 = base_first; base0 < k_old_end; base0 += UNR * STEP)
     {
@@ -439,7 +526,7 @@ DEV void attn_fused_body(const FusedArgs& a, const int kh, const int split, cons
         const int rr = r0 + r;
         const int j = rr / G, g = rr - j * G;
         const size_t qrow = ((size_t)b * a.s + j) * a.H + kh * G + g;
-        const f16 y = (f16)merge_split_partials<true>(a.part_o, a.part_ml, qrow, a.nsplit, eff, HDIM, d);
+        const f16 y = (f16)fused_merge_split_partials(a.part_o, a.part_ml, qrow, a.nsplit, eff, HDIM, d);
         if (DEP && a.sync_signal) store_agent_f16(a.out + fused_out_index<HDIM>(a, qrow, d), y);
         else a.out[fused_out_index<HDIM>(a, qrow, d)] = y;
         if (a.out_nat) a.out_nat[qrow * HDIM + d] = y;

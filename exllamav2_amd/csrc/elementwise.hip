@@ -268,12 +268,33 @@ KERNEL void __launch_bounds__(256) embed_rows_kernel(const f16* table, const int
 
 // embedding row -> x, x times the first consumer's norm weight in that consumer's packed order, and the row's sum of squares
 // (npart = 1): what the chained decode (qgemv_flat.h: A_NORM_PRE) expects from the producer of a residual stream
+// ROPE (the first launch of a chained decode step, exl2_embed_rows_chain_step): the workgroup of sequence `row` also copies the sin and the
+// cos row of the sequence's position -- seqlens[row], the position every layer of this step rotates by -- to rope_now[row][0 | 1][hd]:
+// the attention launches then take their rotary row at level 1 instead of looking it up behind the length, 32 times per step
+// (attn_fused_body.h: ROPE_NOW).  seqlens -> rotary row runs beside ids -> embedding row: no dependent level is added here.  Every
+// thread requests (threads beyond 2 * hd / 8 a duplicate), unconditionally, so nothing is waited for before the embedding row's
+// requests; a template parameter, so the other launches keep their code.
+struct RopeNowArgs { const int* seqlens; const f16* sin; const f16* cos; f16* rope_now; int hd; int rows; };
+
+template <bool ROPE>
 KERNEL void __launch_bounds__(256) embed_rows_chain_kernel(const f16* table, const int* ids, f16* out, int hidden, int vocab,
-                                                           const u16* invperm, const f16* next_w, f16* xp, float* ss, int tiled)
+                                                           const u16* invperm, const f16* next_w, f16* xp, float* ss, int tiled,
+                                                           const RopeNowArgs rn)
 {
     SHARED float part[4];
     const int row = bid_x();
     int id = ids ? ids[row] : row;                       // (no ids: row r of `table` -- exl2_publish_rows)
+    f16x8 rope_v;
+    int rope_t = 0;
+    if constexpr (ROPE)
+    {
+        int pos = rn.seqlens[row];
+        pos = pos < 0 ? 0 : (pos >= rn.rows ? rn.rows - 1 : pos);
+        const int per = rn.hd >> 3;
+        rope_t = tid() % (2 * per);                      // [0, per): sin, [per, 2 per): cos
+        const f16* src_r = (rope_t < per ? rn.sin : rn.cos) + (size_t)pos * rn.hd + (size_t)(rope_t % per) * 8;
+        rope_v = *(const f16x8*)src_r;
+    }
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     const f16x8* src = (const f16x8*)(table + (size_t)id * hidden);
     f16x8* dst = out ? (f16x8*)(out + (size_t)row * hidden) : nullptr;
@@ -305,6 +326,7 @@ KERNEL void __launch_bounds__(256) embed_rows_chain_kernel(const f16* table, con
             *dstp = next_w ? (f16)fmaxf(-65504.0f, fminf(f * (float)next_w[idx[e]], 65504.0f)) : v[e];
         }
     }
+    if constexpr (ROPE) if (tid() < 2 * (rn.hd >> 3)) *(f16x8*)(rn.rope_now + (size_t)row * (2 * rn.hd) + (size_t)rope_t * 8) = rope_v;
     sq = wave_allreduce_add(sq);
     if (lane_id() == 0) part[wave_id()] = sq;
     block_sync();
@@ -391,8 +413,32 @@ int exl2_embed_rows_chain(const void* table, const int* ids, void* x, int rows, 
     EXL2_REQUIRE(hidden % 8 == 0, "embed_rows_chain: hidden %d must be a multiple of 8", hidden);
     EXL2_REQUIRE(!next_invperm || (((size_t)next_invperm) & 15) == 0, "embed_rows_chain: invperm must be 16-byte aligned");
     if (rows <= 0) return EXL2_OK;
-    LAUNCH(embed_rows_chain_kernel, dim3((unsigned)rows), dim3(256), 0, stream, (const f16*)table, ids, (f16*)x, hidden, vocab,
-           (const u16*)next_invperm, (const f16*)next_norm_w, (f16*)xp_out, ss_out, chain_xp_tiled() ? 1 : 0);
+    LAUNCH(embed_rows_chain_kernel<false>, dim3((unsigned)rows), dim3(256), 0, stream, (const f16*)table, ids, (f16*)x, hidden, vocab,
+           (const u16*)next_invperm, (const f16*)next_norm_w, (f16*)xp_out, ss_out, chain_xp_tiled() ? 1 : 0, RopeNowArgs{});
+    HIP_TRY(hipGetLastError());
+    return EXL2_OK;
+}
+
+// exl2_embed_rows_chain as the first launch of a chained decode step: also leaves the rotary rows of the step in rope_now
+// [rows, 2, head_dim] -- the sin and the cos row (tables [sincos_rows, head_dim]) of position cache_seqlens[row], clamped to the table.
+// With rope_now null it is exl2_embed_rows_chain.
+int exl2_embed_rows_chain_step(const void* table, const int* ids, void* x, int rows, int hidden, int vocab,
+                               const void* next_invperm, const void* next_norm_w, void* xp_out, float* ss_out,
+                               const int* cache_seqlens, const void* sin, const void* cos, int sincos_rows, int head_dim,
+                               void* rope_now, void* stream)
+{
+    if (!rope_now)
+        return exl2_embed_rows_chain(table, ids, x, rows, hidden, vocab, next_invperm, next_norm_w, xp_out, ss_out, stream);
+    EXL2_REQUIRE(table && ids && x && xp_out && ss_out, "embed_rows_chain_step: null argument");
+    EXL2_REQUIRE(cache_seqlens && sin && cos, "embed_rows_chain_step: rope_now needs cache_seqlens and the sin / cos tables");
+    EXL2_REQUIRE(hidden % 8 == 0, "embed_rows_chain_step: hidden %d must be a multiple of 8", hidden);
+    EXL2_REQUIRE(head_dim > 0 && head_dim % 8 == 0 && head_dim <= 512 && sincos_rows > 0, "embed_rows_chain_step: head_dim %d / %d table rows", head_dim, sincos_rows);
+    EXL2_REQUIRE(!next_invperm || (((size_t)next_invperm) & 15) == 0, "embed_rows_chain_step: invperm must be 16-byte aligned");
+    EXL2_REQUIRE(((((size_t)sin) | ((size_t)cos) | ((size_t)rope_now)) & 15) == 0, "embed_rows_chain_step: sin / cos / rope_now must be 16-byte aligned");
+    if (rows <= 0) return EXL2_OK;
+    RopeNowArgs rn{cache_seqlens, (const f16*)sin, (const f16*)cos, (f16*)rope_now, head_dim, sincos_rows};
+    LAUNCH(embed_rows_chain_kernel<true>, dim3((unsigned)rows), dim3(256), 0, stream, (const f16*)table, ids, (f16*)x, hidden, vocab,
+           (const u16*)next_invperm, (const f16*)next_norm_w, (f16*)xp_out, ss_out, chain_xp_tiled() ? 1 : 0, rn);
     HIP_TRY(hipGetLastError());
     return EXL2_OK;
 }
@@ -407,8 +453,8 @@ int exl2_publish_rows(const void* x, int rows, int hidden, const void* next_invp
     EXL2_REQUIRE(hidden % 8 == 0, "publish_rows: hidden %d must be a multiple of 8", hidden);
     EXL2_REQUIRE(!next_invperm || (((size_t)next_invperm) & 15) == 0, "publish_rows: invperm must be 16-byte aligned");
     if (rows <= 0) return EXL2_OK;
-    LAUNCH(embed_rows_chain_kernel, dim3((unsigned)rows), dim3(256), 0, stream, (const f16*)x, (const int*)nullptr, (f16*)nullptr, hidden, rows,
-           (const u16*)next_invperm, (const f16*)next_norm_w, (f16*)xp_out, ss_out, chain_xp_tiled() ? 1 : 0);
+    LAUNCH(embed_rows_chain_kernel<false>, dim3((unsigned)rows), dim3(256), 0, stream, (const f16*)x, (const int*)nullptr, (f16*)nullptr, hidden, rows,
+           (const u16*)next_invperm, (const f16*)next_norm_w, (f16*)xp_out, ss_out, chain_xp_tiled() ? 1 : 0, RopeNowArgs{});
     HIP_TRY(hipGetLastError());
     return EXL2_OK;
 }

@@ -601,11 +601,14 @@ class ExtC:
 
     def attn_decode_fused(self, q, k_new, v_new, k_cache, v_cache, out, sin, cos, cache_seqlens, block_table,
                           past_const: int, rope_style: int, scratch, counters, softmax_scale: float | None = None,
-                          sincos_size: int = 0, nsplit: int = 0, out_invperm: int | None = None, head_norm=None) -> bool:
+                          sincos_size: int = 0, nsplit: int = 0, out_invperm: int | None = None, head_norm=None,
+                          rope_now=None, identity_table: bool = False) -> bool:
         """One launch for RoPE + append + attention + merge; False when the shape needs the three-launch path.
         out_invperm (device pointer, u16 [H * hd]): write the output in o_proj's packed order (chained decode).
         head_norm = (q_norm, k_norm, eps, rms) -- fp16 tensors or raw device pointers: the q / k head norm folded into the launch
-        (exl2_attn_decode_fused_norm); q / k_new stay un-normalised."""
+        (exl2_attn_decode_fused_norm); q / k_new stay un-normalised.
+        rope_now (fp16 [b, 2, hd], filled by embed_rows_chain(rope_now=...) for this step) / identity_table (block_table[b][p] ==
+        b * pages_per_seq + p): the chained step's form of the launch (exl2_attn_decode_fused_step)."""
         b, s, nh, hd = q.shape
         kvh = k_new.shape[2]
         page_size = k_cache.shape[1]
@@ -621,12 +624,17 @@ class ExtC:
             float(scale), int(rope_style), int(sincos_size), int(nsplit), self._ptr(scratch), sb,
             self._ptr(counters, torch.int32, "counters"), 0 if counters is None else counters.numel(),
             out_invperm or None)
-        if head_norm is None:
+        if head_norm is None and rope_now is None and not identity_table:
             return self.lib.check(self.lib.exl2_attn_decode_fused(*args, self._stream(q))) == 0
-        qn, kn, eps, rms = head_norm
-        if not isinstance(qn, int):
+        qn, kn, eps, rms = head_norm if head_norm is not None else (None, None, 0.0, True)
+        if qn is not None and not isinstance(qn, int):
             if tuple(qn.shape) != (nh, hd) or tuple(kn.shape) != (kvh, hd): raise RuntimeError("attn_decode_fused: head-norm weight shapes")
             qn, kn = self._ptr(qn, torch.float16, "q_norm"), self._ptr(kn, torch.float16, "k_norm")
+        if rope_now is not None or identity_table:
+            if rope_now is not None and tuple(rope_now.shape) != (b, 2, hd): raise RuntimeError("attn_decode_fused: rope_now shape")
+            return self.lib.check(self.lib.exl2_attn_decode_fused_step(
+                *args, qn, kn, float(eps), int(bool(rms)), self._ptr(rope_now, torch.float16, "rope_now"), int(bool(identity_table)),
+                self._stream(q))) == 0
         return self.lib.check(self.lib.exl2_attn_decode_fused_norm(*args, qn, kn, float(eps), int(bool(rms)), self._stream(q))) == 0
 
     def flash_attn_with_kvcache(self, q, k_cache, v_cache, k=None, v=None, cache_seqlens=None, block_table=None,
@@ -854,7 +862,18 @@ class ExtC:
         """5..16 rows: the chain's xp buffers in the MFMA-tiled layout between (True) and (False) (include/exl2_hip.h)"""
         self.lib.check(self.lib.exl2_chain_set_tiled(1 if on else 0))
 
-    def embed_rows_chain(self, table, ids, x, next_invperm, next_norm_w, xp_out, ss_out) -> None:
+    def embed_rows_chain(self, table, ids, x, next_invperm, next_norm_w, xp_out, ss_out, cache_seqlens=None, sin=None, cos=None,
+                         rope_now=None) -> None:
+        """rope_now (fp16 [rows, 2, head_dim]): also filled with the sin / cos rows of positions cache_seqlens[r] (exl2_embed_rows_chain_step)"""
+        if rope_now is not None:
+            if tuple(rope_now.shape) != (ids.numel(), 2, sin.shape[1]) or sin.shape != cos.shape: raise RuntimeError("embed_rows_chain: rope_now shape")
+            self.lib.check(self.lib.exl2_embed_rows_chain_step(
+                self._ptr(table, torch.float16, "table"), self._ptr(ids, torch.int32, "ids"), self._ptr(x, torch.float16, "x"),
+                ids.numel(), table.shape[1], table.shape[0], next_invperm or None, self._w_ptr(next_norm_w),
+                self._ptr(xp_out, torch.float16, "xp_out"), self._ptr(ss_out, torch.float32, "ss_out"),
+                self._ptr(cache_seqlens, torch.int32, "cache_seqlens"), self._ptr(sin, torch.float16, "sin"), self._ptr(cos, torch.float16, "cos"),
+                sin.shape[0], sin.shape[1], self._ptr(rope_now, torch.float16, "rope_now"), self._stream(x)))
+            return
         self.lib.check(self.lib.exl2_embed_rows_chain(
             self._ptr(table, torch.float16, "table"), self._ptr(ids, torch.int32, "ids"), self._ptr(x, torch.float16, "x"),
             ids.numel(), table.shape[1], table.shape[0], next_invperm or None, self._w_ptr(next_norm_w),

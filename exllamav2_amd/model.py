@@ -267,6 +267,9 @@ class GreedyGraphDecoder:
             "ss_a": torch.zeros((self.b, 512), dtype=torch.float32, device=dev),
             "ss_b": torch.zeros((self.b, 512), dtype=torch.float32, device=dev),
         }
+        # the rotary rows of the step's position, looked up once by the step's first launch for all layers (csrc/attn_fused_body.h: ROPE_NOW)
+        if cfg.rope_style == 2 and m.sin is not None and tuple(m.sin.shape[1:]) == (cfg.head_dim,) and not getattr(self.cache, "wbits", 0):
+            self.chain["rope_now"] = torch.zeros((self.b, 2, cfg.head_dim), dtype=torch.float16, device=dev)
         # 5-16 sequences (round 4): every q_gemm launch runs on the lean kernel, whose ROWS form stages the whole rows once per
         # workgroup when rows x (K + 8) x 2 bytes fit in LDS (csrc/qgemv_lean.hip) -- launches with a larger K (down_proj) run as
         # row groups, each group streaming the weights again (the later ones from the memory-side cache).  EXL2_CHAIN_ROWGROUPS=N
@@ -338,7 +341,9 @@ class GreedyGraphDecoder:
             ext.chain_set_tiled(True)
         try:
             for r0, r1 in groups:
-                ext.embed_rows_chain(m.embed_tokens, self.ids[r0:r1], x2[r0:r1], plan[0][0], plan[0][3], xp_a[r0:r1], pa.out(r0, r1))
+                rn = ch.get("rope_now")
+                ext.embed_rows_chain(m.embed_tokens, self.ids[r0:r1], x2[r0:r1], plan[0][0], plan[0][3], xp_a[r0:r1], pa.out(r0, r1),
+                                     self.cache_seqlens[r0:r1], m.sin, m.cos, None if rn is None else rn[r0:r1])
                 pa.done(1)
         except Exception:
             ext.chain_set_tiled(False)
@@ -358,7 +363,9 @@ class GreedyGraphDecoder:
                 for r0, r1 in groups_h:
                     ss, cnt = pa.inp(r0, r1, "q|k|v")
                     ext.q_attn_forward_1_chain(attn.q_handle, xp_a[r0:r1], ss, cnt, r1 - r0, q[r0:r1], k[r0:r1], v[r0:r1], skip_head_norm=skip_hn)
-                ao = attn.attend_chain(q, k, v, self.cache, self.cache_seqlens, self.block_table, o_inv, head_norm_pending=skip_hn)
+                # (self.block_table is the identity: the launch may address the rows directly)
+                ao = attn.attend_chain(q, k, v, self.cache, self.cache_seqlens, self.block_table, o_inv, head_norm_pending=skip_hn,
+                                       rope_now=ch.get("rope_now"), identity_table=True)
                 # every producer of the residual stream publishes it times its consumer's norm weight, in that consumer's order
                 nxt, nxt_w = (plan[i + 1][0], plan[i + 1][3]) if i + 1 < len(plan) else (ch["head_inv"], ch["norm_head"])
                 if in_m == "moe":

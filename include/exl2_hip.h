@@ -206,6 +206,22 @@ int exl2_attn_decode_fused_norm(const void* q, const void* k_new, const void* v_
                                 int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
                                 void* counters, int n_counters, const void* out_invperm,
                                 const void* q_norm, const void* k_norm, float norm_epsilon, int norm_rms, void* stream);
+/* The launch as a step of the chained decode makes it.  q_norm / k_norm: nullable, both or neither (exl2_attn_decode_fused_norm).
+   rope_now: nullable, fp16 [batch, 2, head_dim] -- the sin and the cos row of position cache_seqlens[b], written by
+   exl2_embed_rows_chain_step at the head of the step; at q_len 1 the launch takes its rotary row from there, with its first requests,
+   instead of from sin / cos behind the length (the same values: the result does not change).  identity_table != 0: the caller
+   states that block_table[b][p] == b * pages_per_seq + p (a contiguous cache seen through a table); the launch then addresses rows
+   directly, which lets split 0 request its first batch of cached rows before the length has arrived (launches without a block
+   table always do).  EXL2_ATT_SPEC (bit 0: those rows, bit 1: rope_now; default 3, 0 = neither) is the A/B switch.
+   No reference counterpart. */
+int exl2_attn_decode_fused_step(const void* q, const void* k_new, const void* v_new, void* k_cache, void* v_cache, void* out,
+                                const void* sin, const void* cos, const int* cache_seqlens, const int* block_table,
+                                int batch, int q_len, int num_heads, int num_kv_heads, int head_dim,
+                                int page_size, int pages_per_seq, int past_const, float softmax_scale,
+                                int rope_style, int sincos_size, int nsplit, void* scratch, long long scratch_bytes,
+                                void* counters, int n_counters, const void* out_invperm,
+                                const void* q_norm, const void* k_norm, float norm_epsilon, int norm_rms,
+                                const void* rope_now, int identity_table, void* stream);
 
 /* Decode attention straight from the Q4 KV cache (ExLlamaV2Cache_Q4, cache.py:409-606; format cache_q.cuh:4-185): replaces
    q_to_fp16_kv of the whole live range (cache.py:472-514) + attention over the fp16 temp.  k_new / v_new (nullable, fp16
@@ -377,6 +393,13 @@ int exl2_chain_set_tiled(int on);
 
 int exl2_embed_rows_chain(const void* table, const int* ids, void* x, int rows, int hidden, int vocab,
                           const void* next_invperm, const void* next_norm_w, void* xp_out, float* ss_out, void* stream);
+/* exl2_embed_rows_chain as the first launch of a chained decode step: the workgroup of row r also copies the sin and the cos row
+   (tables fp16 [sincos_rows, head_dim]) of position cache_seqlens[r] (clamped to the table) to rope_now[r][0] / [r][1] (fp16
+   [rows, 2, head_dim]) for the step's attention launches (exl2_attn_decode_fused_step).  rope_now == NULL: exl2_embed_rows_chain. */
+int exl2_embed_rows_chain_step(const void* table, const int* ids, void* x, int rows, int hidden, int vocab,
+                               const void* next_invperm, const void* next_norm_w, void* xp_out, float* ss_out,
+                               const int* cache_seqlens, const void* sin, const void* cos, int sincos_rows, int head_dim,
+                               void* rope_now, void* stream);
 /* The hand-off a chained producer would have left, made from rows x [rows, hidden] that are already in memory: xp_out = x *
    next_norm_w in the consumer's packed order, ss_out[row] = sum of squares of row (npart = 1).  Run by the module chain behind
    the operator boundary when q_attn_forward_1 (ext_qattn.cpp:115-159) / q_mlp_forward_ (ext_qmlp.cpp:87-118) receive a residual
