@@ -39,6 +39,7 @@
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
+#include <vector>
 #include <mutex>
 
 namespace {
@@ -59,6 +60,9 @@ struct Api
     int (*attn_decode_fused_dual)(cvp, cvp, cvp, void*, void*, void*, cvp, cvp, const int*, const int*, int, int, int, int, int, int, int,
                                   int, float, int, int, int, void*, long long, void*, int, cvp, void*, void*);
     long long (*paged_attn_scratch_bytes)(int, int, int);
+    int (*q_attn_forward_1_loras)(void*, cvp, int, int, int, const int*, void*, void*, void*, cvp, cvp, int, int, const uint64_t*, void*);
+    int (*q_attn_forward_2_loras)(void*, void*, cvp, int, int, int, const uint64_t*, void*);
+    int (*q_mlp_forward_loras)(void*, void*, int, int, const uint64_t*, void*);
 };
 Api api;
 void* dll = nullptr;
@@ -138,6 +142,15 @@ struct State
 // one host thread at a time inside the binding (the GIL serialises Python callers already; this also covers callers that release it)
 std::recursive_mutex g_mu;
 #define LOCKED std::lock_guard<std::recursive_mutex> lock_(g_mu)
+
+// the `loras` argument of the module calls: the ids of the adapters to apply (attn.py:1128-1141: [id(lora), ...]), or None / empty
+std::vector<uint64_t> lora_ids(const py::object& loras)
+{
+    std::vector<uint64_t> ids;
+    if (loras.is_none()) return ids;
+    for (py::handle h : loras) ids.push_back(h.cast<uint64_t>());
+    return ids;
+}
 
 void drop_pending() { S.consumer = nullptr; S.pub_x.clear(); }
 void drop_all() { drop_pending(); S.finisher = nullptr; S.fin_x.clear(); S.cur_attn = nullptr; S.cur_q = nullptr; S.packed_for = nullptr; S.attn_out.clear(); S.packed_ptr = nullptr; }
@@ -258,6 +271,9 @@ void init(const std::string& path, bool cpu_ok)
     bind(api.publish_rows, "exl2_publish_rows");
     bind(api.attn_decode_fused_dual, "exl2_attn_decode_fused_dual");
     bind(api.paged_attn_scratch_bytes, "exl2_paged_attn_scratch_bytes");
+    bind(api.q_attn_forward_1_loras, "exl2_q_attn_forward_1_loras");
+    bind(api.q_attn_forward_2_loras, "exl2_q_attn_forward_2_loras");
+    bind(api.q_mlp_forward_loras, "exl2_q_mlp_forward_loras");
     S = State();
     if (const char* e = getenv("EXL2_MODULE_CHAIN")) S.on = atoi(e) != 0;
     if (const char* e = getenv("EXL2_MODULE_CHAIN_VERIFY")) S.verify = atoi(e) != 0;
@@ -271,7 +287,7 @@ void q_attn_forward_1(uintptr_t handle, const at::Tensor& x, int batch_size, int
                       const at::Tensor& cos, const py::object& loras, const py::object& loras_temp)
 {
     LOCKED;
-    if (!loras.is_none() && py::len(loras) > 0) throw std::runtime_error("q_attn_forward_1: LoRA is out of scope of this build");
+    const std::vector<uint64_t> ids = lora_ids(loras);
     void* h = (void*)handle;
     c10::OptionalDeviceGuard guard; if (x.is_cuda()) guard.reset_device(x.device());
     void* stream = stream_of(x);
@@ -280,6 +296,15 @@ void q_attn_forward_1(uintptr_t handle, const at::Tensor& x, int batch_size, int
     const int rows = batch_size * q_len;
     const int hidden = (int)x.size(-1);
     S.cur_attn = nullptr; S.cur_q = nullptr; S.packed_for = nullptr;
+    if (!ids.empty())
+    {
+        // adapters: the plain module call (the chained kernels carry none); nothing published before it is consumed afterwards
+        drop_all();
+        S.n_plain++;
+        check(api.q_attn_forward_1_loras(h, xq, batch_size, q_len, past_len, i32_ptr(past_lens, "past_lens"), q, k, v, any_ptr(sin), any_ptr(cos), 1,
+                                         (int)ids.size(), ids.data(), stream));
+        return;
+    }
     if (chain_rows(rows))
     {
         ModInfo& mi = info_of(h, true);
@@ -399,13 +424,20 @@ void q_attn_forward_2(uintptr_t handle, const at::Tensor& x, const at::Tensor& a
                       const py::object& loras, const py::object& loras_temp)
 {
     LOCKED;
-    if (!loras.is_none() && py::len(loras) > 0) throw std::runtime_error("q_attn_forward_2: LoRA is out of scope of this build");
+    const std::vector<uint64_t> ids = lora_ids(loras);
     void* h = (void*)handle;
     c10::OptionalDeviceGuard guard; if (x.is_cuda()) guard.reset_device(x.device());
     void* stream = stream_of(x);
     void* xq = f16_ptr(x, "x"); void* ao = f16_ptr(attn_output, "attn_output");
     const int rows = batch_size * q_len;
     const int hidden = (int)x.size(-1);
+    if (!ids.empty())
+    {
+        drop_all();                         // (x is written: no hand-off published for it survives, none is published)
+        S.n_plain++;
+        check(api.q_attn_forward_2_loras(h, xq, ao, batch_size, q_len, (int)ids.size(), ids.data(), stream));
+        return;
+    }
     if (chain_rows(rows) && S.packed_for == h && S.attn_out.is(attn_output, rows, stream))
     {
         const Publish p = successor(h, x, hidden);
@@ -431,13 +463,20 @@ void q_attn_forward_2(uintptr_t handle, const at::Tensor& x, const at::Tensor& a
 void q_mlp_forward_(uintptr_t handle, const at::Tensor& x, const py::object& loras, const py::object& loras_temp)
 {
     LOCKED;
-    if (!loras.is_none() && py::len(loras) > 0) throw std::runtime_error("q_mlp_forward_: LoRA is out of scope of this build");
+    const std::vector<uint64_t> ids = lora_ids(loras);
     void* h = (void*)handle;
     c10::OptionalDeviceGuard guard; if (x.is_cuda()) guard.reset_device(x.device());
     void* stream = stream_of(x);
     void* xq = f16_ptr(x, "x");
     const int hidden = (int)x.size(-1);
     const int rows = (int)(x.numel() / hidden);
+    if (!ids.empty())
+    {
+        drop_all();
+        S.n_plain++;
+        check(api.q_mlp_forward_loras(h, xq, rows, (int)ids.size(), ids.data(), stream));
+        return;
+    }
     if (chain_rows(rows))
     {
         ModInfo& mi = info_of(h, false);

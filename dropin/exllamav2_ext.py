@@ -3,7 +3,7 @@ it up instead of JIT-building its CUDA sources (`import exllamav2_ext` succeeds 
 
 Every name of the reference's pybind module (ext_bindings.cpp:27-138) that lies on the quantized forward path is
 forwarded, with the reference's argument order, to the MI355X library through `exllamav2_amd.ext_c` (ctypes over the
-C ABI of include/exl2_hip.h).  Names outside the hot path (sampler chain, quantizer, LoRA, vision) raise
+C ABI of include/exl2_hip.h).  Names outside the hot path (sampler chain, quantizer, vision) raise
 NotImplementedError with the SURVEY.md section that scopes them out -- loudly, never silently.
 """
 import os as _os
@@ -132,9 +132,9 @@ if _fast is not None:
         _fast.note_write(x)
         return _e.rope_(x, sin, cos, past_len, num_heads, head_dim, offsets, neox_style)
 
-    def q_moe_mlp_forward_(q_moe_mlp, x):
+    def q_moe_mlp_forward_(q_moe_mlp, x, loras=None, loras_temp=None):
         _fast.note_write(x)
-        return _e.q_moe_mlp_forward_(q_moe_mlp, x)
+        return _e.q_moe_mlp_forward_(q_moe_mlp, x, loras, loras_temp)
 else:
     q_attn_forward_1 = _e.q_attn_forward_1
     q_attn_forward_2 = _e.q_attn_forward_2
@@ -154,12 +154,24 @@ def set_flash_attn_func():          # ext_qattn.cpp:256-259 is a no-op in the re
     return None
 
 
-def q_attn_set_loras(*a, **k):      # LoRA is out of scope; an empty set is the only accepted state
-    return 0
+def _lora_pairs(lora_a, lora_b):
+    """the reference's two dicts of one projection, {id(lora): A [in, r]} and {id(lora): B [r, out]} (attn.py:1545-1552), as one
+    {id: (A, B, rank)}; an adapter with only one half for a projection has no entry for it"""
+    return {i: (a, lora_b[i], a.shape[1]) for i, a in (lora_a or {}).items() if i in (lora_b or {})}
 
 
-def q_mlp_set_loras(*a, **k):
-    return 0
+def q_attn_set_loras(q_attn, q_proj_lora_a, q_proj_lora_b, k_proj_lora_a, k_proj_lora_b, v_proj_lora_a, v_proj_lora_b,
+                     o_proj_lora_a, o_proj_lora_b):
+    """ext_qattn.cpp:193-254 as attn.py:1554-1564 calls it: replaces the handle's adapter table (the handle copies the tensors);
+    returns the largest rank, by which the caller sizes loras_temp"""
+    return _e.q_attn_set_loras(q_attn, _lora_pairs(q_proj_lora_a, q_proj_lora_b), _lora_pairs(k_proj_lora_a, k_proj_lora_b),
+                               _lora_pairs(v_proj_lora_a, v_proj_lora_b), _lora_pairs(o_proj_lora_a, o_proj_lora_b))
+
+
+def q_mlp_set_loras(q_mlp, gate_proj_lora_a, gate_proj_lora_b, up_proj_lora_a, up_proj_lora_b, down_proj_lora_a, down_proj_lora_b):
+    """ext_qmlp.cpp:120-169 as mlp.py:534-542 calls it"""
+    return _e.q_mlp_set_loras(q_mlp, _lora_pairs(gate_proj_lora_a, gate_proj_lora_b), _lora_pairs(up_proj_lora_a, up_proj_lora_b),
+                              _lora_pairs(down_proj_lora_a, down_proj_lora_b))
 
 
 def _out_of_scope(name, why):

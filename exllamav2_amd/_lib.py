@@ -91,6 +91,16 @@ PROTOTYPES = {
     "exl2_make_q_mlp": (ci, [C.POINTER(vp), vp, vp, ci, cf, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, ci, ci]),
     "exl2_free_q_mlp": (ci, [vp]),
     "exl2_q_mlp_forward": (ci, [vp, vp, ci, vp]),
+    # LoRA adapters (csrc/lora.hip)
+    "exl2_q_attn_set_loras": (ci, [vp, ci, vp, vp, vp, vp]),
+    "exl2_q_mlp_set_loras": (ci, [vp, ci, vp, vp, vp, vp]),
+    "exl2_q_attn_forward_1_loras": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp]),
+    "exl2_q_attn_forward_2_loras": (ci, [vp, vp, vp, ci, ci, ci, vp, vp]),
+    "exl2_q_mlp_forward_loras": (ci, [vp, vp, ci, ci, vp, vp]),
+    "exl2_make_lora_group": (ci, [C.POINTER(vp), ci, ci, vp, ci]),
+    "exl2_free_lora_group": (ci, [vp]),
+    "exl2_lora_group_set_loras": (ci, [vp, ci, vp, vp, vp, vp]),
+    "exl2_apply_loras": (ci, [vp, ci, vp, vp, vp, ci, vp]),
     "exl2_make_q_moe_mlp": (ci, [C.POINTER(vp), vp, vp, ci, cf, vp, ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                  vp, vp, vp, vp, vp, vp, ci, ci]),
     "exl2_free_q_moe_mlp": (ci, [vp]),

@@ -81,18 +81,31 @@ class ExLlamaV2Attention:
         for lin in (self.q_proj, self.k_proj, self.v_proj, self.o_proj):
             lin.unload()
 
-    def forward(self, hidden_states: torch.Tensor, cache, past_len: int = 0, cache_seqlens=None, block_table=None):
+    def update_loras(self) -> int:
+        """attn.py:1545-1566: hands the adapters attached to the four linears to the handle (which copies them); returns the largest rank"""
+        return self.ext.q_attn_set_loras(self.q_handle, self.q_proj.lora_table(), self.k_proj.lora_table(), self.v_proj.lora_table(),
+                                         self.o_proj.lora_table())
+
+    def forward(self, hidden_states: torch.Tensor, cache, past_len: int = 0, cache_seqlens=None, block_table=None, loras=None):
         """In place on hidden_states [b, q_len, hidden] (residual add in o_proj's epilogue).
 
         Contiguous mode (attn.py:1017-1196): scalar `past_len`, cache viewed [b, max_seq_len, kvh, hd].
         Paged mode (attn.py:466-638): `cache_seqlens` int32 [b] + `block_table` int32 [b, pages] on the device,
-        cache viewed [pages, 256, kvh, hd]; positions are read on the device (graph-capturable)."""
+        cache viewed [pages, 256, kvh, hd]; positions are read on the device (graph-capturable).
+        loras: the ExLlamaV2Lora adapters to apply (attn.py:1017-1031)."""
         b, q_len, _ = hidden_states.shape
+        if loras:
+            if type(self) is not ExLlamaV2Attention:
+                raise RuntimeError(f"{type(self).__name__}: LoRA adapters are not built for this attention module")
+            ids = [id(l) for l in loras]
+            q, k, v = self._project_qkv(hidden_states, b, q_len, ids)
+            attn_out = self._attend(q, k, v, cache, past_len, cache_seqlens, block_table)
+            return self._project_out(hidden_states, attn_out, b, q_len, ids)
         q, k, v = self._project_qkv(hidden_states, b, q_len)
         attn_out = self._attend(q, k, v, cache, past_len, cache_seqlens, block_table)
         return self._project_out(hidden_states, attn_out, b, q_len)
 
-    def _project_qkv(self, hidden_states, b: int, q_len: int):
+    def _project_qkv(self, hidden_states, b: int, q_len: int, lora_ids=None):
         """Front half (q_attn_forward_1, q_attn.cu:153-317): RMSNorm + q/k/v projections into the scratch rows; RoPE is
         applied later, inside the attention launch."""
         cfg, m, ext = self.model.config, self.model, self.ext
@@ -101,7 +114,7 @@ class ExLlamaV2Attention:
         k = m.temp_k[:rows].view(b, q_len, cfg.num_key_value_heads, cfg.head_dim)
         v = m.temp_v[:rows].view(b, q_len, cfg.num_key_value_heads, cfg.head_dim)
         ext.q_attn_forward_1(self.q_handle, hidden_states, b, q_len, 0, none_tensor, q, k, v, m.sin, m.cos,
-                             apply_rope=False)
+                             loras=lora_ids, apply_rope=False)
         return q, k, v
 
     def _attend(self, q, k, v, cache, past_len, cache_seqlens, block_table):
@@ -217,8 +230,8 @@ class ExLlamaV2Attention:
             raise RuntimeError("attend_chain: shape not covered by the one-launch attention kernel")
         return attn_out
 
-    def _project_out(self, hidden_states, attn_out, b: int, q_len: int):
+    def _project_out(self, hidden_states, attn_out, b: int, q_len: int, lora_ids=None):
         """Back half (q_attn_forward_2, q_attn.cu:319-345): x += attn_out . Wo"""
-        self.ext.q_attn_forward_2(self.q_handle, hidden_states, attn_out, b, q_len)
+        self.ext.q_attn_forward_2(self.q_handle, hidden_states, attn_out, b, q_len, loras=lora_ids)
         return hidden_states
 

@@ -13,6 +13,8 @@
 #include "qgemv_lean.h"
 #include "chain_sync.h"
 #include "moe.h"
+#include "lora.h"
+#include "qgemv_common.h"
 #include "errors.h"
 #include <string.h>
 #include <stdlib.h>
@@ -75,6 +77,7 @@ struct QAttn
     bool residual_fp32; bool use_graphs;
     bool chain_ok; f16* norm_w_perm;            // chained decode: layernorm gathered through q/k/v's shared q_perm (owned)
     bool qkv_same_perm;                         // q, k, v share one act-order permutation (prefill: rows staged once)
+    LoraGroup* lora_qkv; LoraGroup* lora_o;     // adapter tables (lora.h; owned, made by exl2_q_attn_set_loras)
 };
 
 struct QMLP
@@ -86,6 +89,7 @@ struct QMLP
     const f16* post_layernorm; const f16* post_layernorm_bias; bool residual_fp32; bool use_graphs;
     bool chain_ok; f16* norm_w_perm;            // chained decode: layernorm gathered through gate/up's shared q_perm (owned)
     bool gu_same_perm;                          // gate and up share one act-order permutation (prefill: rows staged once)
+    LoraGroup* lora_gu; LoraGroup* lora_down;   // adapter tables (lora.h; owned, made by exl2_q_mlp_set_loras); gateless: lora_gu = up alone
 };
 
 // true when every matrix carries the same act-order permutation (or none does)
@@ -724,6 +728,7 @@ int exl2_free_q_attn(void* handle)
 {
     QAttn* a = (QAttn*)handle;
     if (a && a->norm_w_perm) (void)hipFree(a->norm_w_perm);
+    if (a) { lora_group_free(a->lora_qkv); lora_group_free(a->lora_o); }
     free(handle);
     return EXL2_OK;
 }
@@ -803,6 +808,99 @@ int exl2_q_attn_forward_2(void* handle, void* x, const void* attn_output, int ba
     return exl2_rms_norm(a->temp_state, a->post_layernorm, x, a->norm_epsilon, rows, a->hidden_size, 1, 0, 0, stream);
 }
 
+// q_attn_set_loras (ext_qattn.cpp:213-251): replaces the handle's adapter table.  a / b / ranks [n_loras * 4], adapter-major, in the
+// order q, k, v, o; a null pointer or rank 0 = no entry (lora.h).  Returns the largest rank.  Load time: synchronises.
+int exl2_q_attn_set_loras(void* handle, int n_loras, const uint64_t* ids, const void* const* a, const void* const* b, const int* ranks)
+{
+    EXL2_REQUIRE(handle && n_loras >= 0 && (n_loras == 0 || (ids && a && b && ranks)), "q_attn_set_loras: null argument");
+    QAttn* at = (QAttn*)handle;
+    EXL2_REQUIRE(at->temp_state || !at->layernorm, "q_attn_set_loras: handle was made without scratch (tensor-parallel load)");
+    if (!at->lora_qkv)
+    {
+        const int N[3] = {at->q_proj->width, at->k_proj->width, at->v_proj->width};
+        const int rc = lora_group_make(&at->lora_qkv, 3, at->hidden_size, N, at->max_rows);
+        if (rc) return rc;
+    }
+    if (!at->lora_o)
+    {
+        const int N[1] = {at->o_proj->width};
+        const int rc = lora_group_make(&at->lora_o, 1, at->o_proj->height, N, at->max_rows);
+        if (rc) return rc;
+    }
+    std::vector<const void*> a3((size_t)n_loras * 3), b3((size_t)n_loras * 3), a1(n_loras), b1(n_loras);
+    std::vector<int> r3((size_t)n_loras * 3), r1(n_loras);
+    for (int l = 0; l < n_loras; l++)
+    {
+        for (int p = 0; p < 3; p++) { a3[l * 3 + p] = a[l * 4 + p]; b3[l * 3 + p] = b[l * 4 + p]; r3[l * 3 + p] = ranks[l * 4 + p]; }
+        a1[l] = a[l * 4 + 3]; b1[l] = b[l * 4 + 3]; r1[l] = ranks[l * 4 + 3];
+    }
+    const int m3 = lora_group_set(at->lora_qkv, n_loras, (const u64*)ids, a3.data(), b3.data(), r3.data());
+    if (m3 < 0) return m3;
+    const int m1 = lora_group_set(at->lora_o, n_loras, (const u64*)ids, a1.data(), b1.data(), r1.data());
+    if (m1 < 0) return m1;
+    return m3 > m1 ? m3 : m1;
+}
+
+// q_attn_forward_1 with the `loras` list (ext_qattn.cpp:115-159).  An empty list is exl2_q_attn_forward_1, launch for launch.  Otherwise
+// the reference's unfused sequence (q_attn.cu:266-283), so that the rows the adapters read exist in memory: RMSNorm into temp_state,
+// q | k | v from temp_state, the adapters of the listed ids on temp_q / k / v (one launch pair), then head norm / RoPE as above.
+int exl2_q_attn_forward_1_loras(void* handle, const void* x, int batch_size, int q_len, int past_len, const int* past_lens,
+                                void* temp_q, void* temp_k, void* temp_v, const void* sin, const void* cos, int apply_rope,
+                                int n_loras, const uint64_t* lora_ids, void* stream)
+{
+    if (n_loras <= 0) return exl2_q_attn_forward_1(handle, x, batch_size, q_len, past_len, past_lens, temp_q, temp_k, temp_v, sin, cos, apply_rope, stream);
+    EXL2_REQUIRE(handle && x && temp_q && temp_k && temp_v && lora_ids, "q_attn_forward_1: null argument");
+    EXL2_REQUIRE(!chain_sync_active(), "q_attn_forward_1: adapters are not built for the overlapped chain");
+    QAttn* a = (QAttn*)handle;
+    const int rows = batch_size * q_len;
+    if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(a->temp_state || !a->layernorm, "q_attn_forward_1: handle was made without scratch (tensor-parallel load)");
+    EXL2_REQUIRE(rows <= a->max_rows, "q_attn_forward_1: %d rows exceed max_rows %d", rows, a->max_rows);
+    const bool gptq = a->q_proj->is_gptq;
+    EXL2_REQUIRE(a->k_proj->is_gptq == gptq && a->v_proj->is_gptq == gptq, "q_attn_forward_1: mixed EXL2/GPTQ projections");
+    const f16* ns = (const f16*)x;
+    if (a->layernorm)
+    {
+        const int rc = exl2_rms_norm(x, a->layernorm, a->temp_state, a->norm_epsilon, rows, a->hidden_size, 0, 0, 0, stream);
+        if (rc) return rc;
+        ns = a->temp_state;
+    }
+    GemvJob jobs[3];
+    fill_job(jobs[0], a->q_proj, ns, (f16*)temp_q, A_PLAIN, C_STORE);
+    fill_job(jobs[1], a->k_proj, ns, (f16*)temp_k, A_PLAIN, C_STORE);
+    fill_job(jobs[2], a->v_proj, ns, (f16*)temp_v, A_PLAIN, C_STORE);
+    jobs[1].rows_as_prev = jobs[2].rows_as_prev = a->qkv_same_perm ? 1 : 0;
+    LAUNCH_JOBS(jobs, 3, rows, gptq, stream, "q_attn_forward_1");
+    {
+        f16* const outs[3] = {(f16*)temp_q, (f16*)temp_k, (f16*)temp_v};
+        const int rc = lora_group_apply(a->lora_qkv, n_loras, (const u64*)lora_ids, ns, outs, rows, stream);
+        if (rc) return rc;
+    }
+    if (a->q_norm) return q_attn_head_norm(a, batch_size, q_len, past_len, past_lens, temp_q, temp_k, sin, cos, apply_rope, stream, "q_attn_forward_1");
+    if (apply_rope && a->rope_style != 0)
+    {
+        EXL2_REQUIRE(sin && cos, "q_attn_forward_1: sin/cos tables missing");
+        return exl2_rope_qk(temp_q, temp_k, sin, cos, batch_size, q_len * a->num_heads, q_len * a->num_kv_heads,
+                            a->head_dim, a->num_heads, a->num_kv_heads, past_len, past_lens, a->rope_style == 2,
+                            a->sincos_size, stream);
+    }
+    return EXL2_OK;
+}
+
+// q_attn_forward_2 with the `loras` list (ext_qattn.cpp:161-191): o_proj as above, then the adapters on x reading attn_output -- behind
+// the post-norm branch too (q_attn.cu:344)
+int exl2_q_attn_forward_2_loras(void* handle, void* x, const void* attn_output, int batch_size, int q_len, int n_loras,
+                                const uint64_t* lora_ids, void* stream)
+{
+    const int rc = exl2_q_attn_forward_2(handle, x, attn_output, batch_size, q_len, stream);
+    if (rc || n_loras <= 0 || batch_size * q_len <= 0) return rc;
+    EXL2_REQUIRE(lora_ids, "q_attn_forward_2: null argument");
+    EXL2_REQUIRE(!chain_sync_active(), "q_attn_forward_2: adapters are not built for the overlapped chain");
+    QAttn* a = (QAttn*)handle;
+    f16* const outs[1] = {(f16*)x};
+    return lora_group_apply(a->lora_o, n_loras, (const u64*)lora_ids, (const f16*)attn_output, outs, batch_size * q_len, stream);
+}
+
 // make_q_mlp (ext_qmlp.h; call site mlp.py:204-223)
 int exl2_make_q_mlp(void** handle, const void* layernorm, const void* layernorm_bias, int layernorm_is_rms,
                     float norm_epsilon, void* q_gate, void* q_up, void* q_down, void* temp_state, void* temp_a,
@@ -839,6 +937,7 @@ int exl2_free_q_mlp(void* handle)
 {
     QMLP* m = (QMLP*)handle;
     if (m && m->norm_w_perm) (void)hipFree(m->norm_w_perm);
+    if (m) { lora_group_free(m->lora_gu); lora_group_free(m->lora_down); }
     free(handle);
     return EXL2_OK;
 }
@@ -884,6 +983,115 @@ int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream)
     if (m->post_layernorm)
         return exl2_rms_norm(m->temp_state, m->post_layernorm, x, m->norm_epsilon, rows, hidden, 1, 0, 0, stream);
     return EXL2_OK;
+}
+
+// x = act(x) in place, fp16 [rows, width] (the gateless MLP with adapters: fp_act_kernel of q_mlp.cu:212-213; without adapters the
+// activation rides in down's staging)
+KERNEL void __launch_bounds__(256) act_rows_kernel(f16* x, long long n8, int gelu)
+{
+    const long long i = (long long)bid_x() * 256 + tid();
+    if (i >= n8) return;
+    f16x8 v = ((const f16x8*)x)[i];
+    #pragma unroll
+    for (int e = 0; e < 8; e++) v[e] = act_h(v[e], gelu != 0);
+    ((f16x8*)x)[i] = v;
+}
+
+// q_mlp_set_loras (ext_qmlp.cpp:120-152): a / b / ranks [n_loras * 3], adapter-major, in the order gate, up, down (a gateless handle
+// ignores the gate entries); otherwise as exl2_q_attn_set_loras
+int exl2_q_mlp_set_loras(void* handle, int n_loras, const uint64_t* ids, const void* const* a, const void* const* b, const int* ranks)
+{
+    EXL2_REQUIRE(handle && n_loras >= 0 && (n_loras == 0 || (ids && a && b && ranks)), "q_mlp_set_loras: null argument");
+    QMLP* m = (QMLP*)handle;
+    EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
+                 "q_mlp_set_loras: handle was made without scratch (tensor-parallel load)");
+    const int n_gu = m->gate ? 2 : 1;
+    if (!m->lora_gu)
+    {
+        const int N[2] = {m->gate ? m->gate->width : m->up->width, m->up->width};
+        const int rc = lora_group_make(&m->lora_gu, n_gu, m->up->height, N, m->max_rows);
+        if (rc) return rc;
+    }
+    if (!m->lora_down)
+    {
+        const int N[1] = {m->down->width};
+        const int rc = lora_group_make(&m->lora_down, 1, m->down->height, N, m->max_rows);
+        if (rc) return rc;
+    }
+    std::vector<const void*> ag((size_t)n_loras * n_gu), bg((size_t)n_loras * n_gu), ad(n_loras), bd(n_loras);
+    std::vector<int> rg((size_t)n_loras * n_gu), rd(n_loras);
+    for (int l = 0; l < n_loras; l++)
+    {
+        for (int p = 0; p < n_gu; p++)
+        {
+            const int src = l * 3 + (m->gate ? p : 1);
+            ag[l * n_gu + p] = a[src]; bg[l * n_gu + p] = b[src]; rg[l * n_gu + p] = ranks[src];
+        }
+        ad[l] = a[l * 3 + 2]; bd[l] = b[l * 3 + 2]; rd[l] = ranks[l * 3 + 2];
+    }
+    const int mg = lora_group_set(m->lora_gu, n_loras, (const u64*)ids, ag.data(), bg.data(), rg.data());
+    if (mg < 0) return mg;
+    const int md = lora_group_set(m->lora_down, n_loras, (const u64*)ids, ad.data(), bd.data(), rd.data());
+    if (md < 0) return md;
+    return mg > md ? mg : md;
+}
+
+// q_mlp_forward_ with the `loras` list (ext_qmlp.cpp:87-118).  An empty list is exl2_q_mlp_forward, launch for launch.  Otherwise the
+// reference's unfused sequence (q_mlp.cu:176-235): RMSNorm into temp_state, gate | up into temp_a / temp_b in their natural column
+// order, their adapters, act(gate) * up in place, down_proj from temp_a, then down's adapters on x reading temp_a.
+int exl2_q_mlp_forward_loras(void* handle, void* x, int rows, int n_loras, const uint64_t* lora_ids, void* stream)
+{
+    if (n_loras <= 0) return exl2_q_mlp_forward(handle, x, rows, stream);
+    EXL2_REQUIRE(handle && x && lora_ids, "q_mlp_forward_: null argument");
+    EXL2_REQUIRE(!chain_sync_active(), "q_mlp_forward_: adapters are not built for the overlapped chain");
+    QMLP* m = (QMLP*)handle;
+    if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(rows <= m->max_rows, "q_mlp_forward_: %d rows exceed max_rows %d", rows, m->max_rows);
+    EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
+                 "q_mlp_forward_: handle was made without scratch (tensor-parallel load)");
+    const int hidden = m->up->height, inter = m->up->width;
+    const bool gptq = m->up->is_gptq;
+    const f16* ns = (const f16*)x;
+    if (m->layernorm)
+    {
+        const int rc = exl2_rms_norm(x, m->layernorm, m->temp_state, m->norm_epsilon, rows, hidden, 0, 0, 0, stream);
+        if (rc) return rc;
+        ns = m->temp_state;
+    }
+    GemvJob jobs[2];
+    int n = 0;
+    if (m->gate) { fill_job(jobs[n], m->gate, ns, m->temp_a, A_PLAIN, C_STORE); n++; fill_job(jobs[n], m->up, ns, m->temp_b, A_PLAIN, C_STORE); n++; }
+    else         { fill_job(jobs[n], m->up, ns, m->temp_a, A_PLAIN, C_STORE); n++; }
+    if (n == 2) jobs[1].rows_as_prev = m->gu_same_perm ? 1 : 0;
+    LAUNCH_JOBS(jobs, n, rows, gptq, stream, "q_mlp_forward_");
+    {
+        f16* const outs[2] = {m->temp_a, m->temp_b};
+        const int rc = lora_group_apply(m->lora_gu, n_loras, (const u64*)lora_ids, ns, outs, rows, stream);
+        if (rc) return rc;
+    }
+    if (m->gate)
+    {
+        const int rc = exl2_act_mul(m->temp_a, m->temp_b, rows, inter, m->act_gelu ? 1 : 0, nullptr, 0, stream);
+        if (rc) return rc;
+    }
+    else
+    {
+        EXL2_REQUIRE(inter % 8 == 0, "q_mlp_forward_: width %d must be a multiple of 8", inter);
+        const long long n8 = (long long)rows * inter / 8;
+        LAUNCH(act_rows_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, m->temp_a, n8, m->act_gelu ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    GemvJob d;
+    fill_job(d, m->down, m->temp_a, m->post_layernorm ? m->temp_state : (f16*)x, A_PLAIN,
+             (m->post_layernorm || !m->has_residual) ? C_STORE : C_ACCUM);
+    LAUNCH_JOBS(&d, 1, rows, m->down->is_gptq, stream, "q_mlp_forward_");
+    if (m->post_layernorm)
+    {
+        const int rc = exl2_rms_norm(m->temp_state, m->post_layernorm, x, m->norm_epsilon, rows, hidden, 1, 0, 0, stream);
+        if (rc) return rc;
+    }
+    f16* const outs[1] = {(f16*)x};
+    return lora_group_apply(m->lora_down, n_loras, (const u64*)lora_ids, m->temp_a, outs, rows, stream);
 }
 
 

@@ -671,15 +671,25 @@ class ExtC:
 
     def q_attn_forward_1(self, q_attn, x, batch_size, q_len, past_len, past_lens, q_temp, k_temp, v_temp, sin, cos,
                          loras=None, loras_temp=None, apply_rope: bool = True) -> None:
-        if loras: raise RuntimeError("q_attn_forward_1: LoRA is out of scope of this build")
-        self.lib.check(self.lib.exl2_q_attn_forward_1(
-            q_attn, self._ptr(x, torch.float16, "x"), int(batch_size), int(q_len), int(past_len),
-            self._ptr(past_lens, torch.int32, "past_lens"), self._ptr(q_temp, torch.float16, "q_temp"),
-            self._ptr(k_temp, torch.float16, "k_temp"), self._ptr(v_temp, torch.float16, "v_temp"),
-            self._ptr(sin), self._ptr(cos), int(apply_rope), self._stream(x)))
+        """loras: the ids of the adapters to apply (q_attn_set_loras), any iterable of ints; loras_temp is accepted and unused (the
+        handle keeps its own scratch)."""
+        args = (q_attn, self._ptr(x, torch.float16, "x"), int(batch_size), int(q_len), int(past_len),
+                self._ptr(past_lens, torch.int32, "past_lens"), self._ptr(q_temp, torch.float16, "q_temp"),
+                self._ptr(k_temp, torch.float16, "k_temp"), self._ptr(v_temp, torch.float16, "v_temp"),
+                self._ptr(sin), self._ptr(cos), int(apply_rope))
+        if loras:
+            n, ids = self._lora_ids(loras)
+            self.lib.check(self.lib.exl2_q_attn_forward_1_loras(*args, n, ids, self._stream(x)))
+            return
+        self.lib.check(self.lib.exl2_q_attn_forward_1(*args, self._stream(x)))
 
     def q_attn_forward_2(self, q_attn, x, attn_output, batch_size, q_len, loras=None, loras_temp=None) -> None:
-        if loras: raise RuntimeError("q_attn_forward_2: LoRA is out of scope of this build")
+        if loras:
+            n, ids = self._lora_ids(loras)
+            self.lib.check(self.lib.exl2_q_attn_forward_2_loras(q_attn, self._ptr(x, torch.float16, "x"),
+                                                                self._ptr(attn_output, torch.float16, "attn_output"),
+                                                                int(batch_size), int(q_len), n, ids, self._stream(x)))
+            return
         self.lib.check(self.lib.exl2_q_attn_forward_2(q_attn, self._ptr(x, torch.float16, "x"),
                                                       self._ptr(attn_output, torch.float16, "attn_output"),
                                                       int(batch_size), int(q_len), self._stream(x)))
@@ -699,10 +709,71 @@ class ExtC:
         self.lib.check(self.lib.exl2_free_q_mlp(handle))
 
     def q_mlp_forward_(self, q_mlp, x, loras=None, loras_temp=None) -> None:
-        if loras: raise RuntimeError("q_mlp_forward_: LoRA is out of scope of this build")
         hidden = x.shape[-1]
+        if loras:
+            n, ids = self._lora_ids(loras)
+            self.lib.check(self.lib.exl2_q_mlp_forward_loras(q_mlp, self._ptr(x, torch.float16, "x"), x.numel() // hidden, n, ids,
+                                                             self._stream(x)))
+            return
         self.lib.check(self.lib.exl2_q_mlp_forward(q_mlp, self._ptr(x, torch.float16, "x"), x.numel() // hidden,
                                                    self._stream(x)))
+
+    # ---- LoRA adapters (ext_qattn.cpp:193-254, ext_qmlp.cpp:120-169; csrc/lora.hip) ------------------------------------------
+
+    @staticmethod
+    def _lora_ids(loras):
+        ids = [int(i) for i in loras]
+        return len(ids), (C.c_uint64 * len(ids))(*ids)
+
+    def _lora_table(self, what: str, projections) -> tuple:
+        """projections: one {id: (A [K, r] fp16, B [r, N] fp16)} dict per projection (the reference also stores a rank as a third
+        element: accepted, the tensor's own shape is what counts).  -> (n, ids, a, b, ranks) in the C ABI's adapter-major layout."""
+        ids = []
+        for d in projections:
+            for i in d:
+                if int(i) not in ids: ids.append(int(i))
+        np_ = len(projections)
+        n = len(ids)
+        a, b, r = (C.c_void_p * max(1, n * np_))(), (C.c_void_p * max(1, n * np_))(), (C.c_int * max(1, n * np_))()
+        for li, i in enumerate(ids):
+            for pi, d in enumerate(projections):
+                ent = d.get(i)
+                if ent is None: continue
+                ta, tb = ent[0], ent[1]
+                if ta.dim() != 2 or tb.dim() != 2 or ta.shape[1] != tb.shape[0]:
+                    raise RuntimeError(f"{what}: adapter {i}: A [K, r] and B [r, N] expected, got {tuple(ta.shape)} and {tuple(tb.shape)}")
+                a[li * np_ + pi] = self._ptr(ta, torch.float16, "lora_a")
+                b[li * np_ + pi] = self._ptr(tb, torch.float16, "lora_b")
+                r[li * np_ + pi] = int(ta.shape[1])
+        return n, (C.c_uint64 * max(1, n))(*ids), a, b, r
+
+    def q_attn_set_loras(self, q_attn, q_proj: dict, k_proj: dict, v_proj: dict, o_proj: dict) -> int:
+        """Replaces the handle's adapter table (the handle copies the tensors); returns the largest rank."""
+        return self.lib.check(self.lib.exl2_q_attn_set_loras(q_attn, *self._lora_table("q_attn_set_loras", [q_proj, k_proj, v_proj, o_proj])))
+
+    def q_mlp_set_loras(self, q_mlp, gate_proj: dict, up_proj: dict, down_proj: dict) -> int:
+        return self.lib.check(self.lib.exl2_q_mlp_set_loras(q_mlp, *self._lora_table("q_mlp_set_loras", [gate_proj, up_proj, down_proj])))
+
+    def make_lora_group(self, in_features: int, out_features, max_rows: int) -> int:
+        """A group of 1 .. 3 projections [in_features, out_features[p]] reading the same rows, on its own (operator-level use)."""
+        h = C.c_void_p()
+        n = (C.c_int * len(out_features))(*[int(v) for v in out_features])
+        self.lib.check(self.lib.exl2_make_lora_group(C.byref(h), len(out_features), int(in_features), n, int(max_rows)))
+        return int(h.value)
+
+    def free_lora_group(self, handle: int) -> None:
+        self.lib.check(self.lib.exl2_free_lora_group(handle))
+
+    def lora_group_set_loras(self, handle: int, projections) -> int:
+        return self.lib.check(self.lib.exl2_lora_group_set_loras(handle, *self._lora_table("lora_group_set_loras", list(projections))))
+
+    def apply_loras(self, handle: int, loras, x, outputs) -> None:
+        """outputs[p] [rows, N_p] += sum over the listed adapters of fp16(x A) B, for every projection of the group (None where the
+        caller knows that no listed adapter has an entry)."""
+        n, ids = self._lora_ids(loras)
+        outs = (C.c_void_p * len(outputs))(*[self._ptr(o, torch.float16, "output") for o in outputs])
+        self.lib.check(self.lib.exl2_apply_loras(handle, n, ids, self._ptr(x, torch.float16, "x"), outs, x.numel() // x.shape[-1],
+                                                 self._stream(x)))
 
     # ---- MoE (ext_qmlp.cpp:245-272) -------------------------------------------------------------------------------------
 
@@ -723,8 +794,9 @@ class ExtC:
     def free_q_moe_mlp(self, handle: int) -> None:
         self.lib.check(self.lib.exl2_free_q_moe_mlp(handle))
 
-    def q_moe_mlp_forward_(self, q_moe_mlp, x) -> None:
+    def q_moe_mlp_forward_(self, q_moe_mlp, x, loras=None, loras_temp=None) -> None:
         """In place on x [rows, hidden] (any row count up to max_rows; the reference's fused path stops at 4)."""
+        if loras: raise RuntimeError("q_moe_mlp_forward_: adapters on MoE experts are not built (the reference's are commented out too)")
         hidden = x.shape[-1]
         self.lib.check(self.lib.exl2_q_moe_mlp_forward(q_moe_mlp, self._ptr(x, torch.float16, "x"), x.numel() // hidden,
                                                        self._stream(x)))
@@ -761,16 +833,18 @@ class ExtC:
         self.lib.check(self.lib.exl2_q_matrix_perm_info(q_handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def q_attn_forward_1_chain(self, q_attn, xp, ss, npart: int, rows: int, q_temp, k_temp, v_temp, skip_head_norm: bool = False) -> None:
+    def q_attn_forward_1_chain(self, q_attn, xp, ss, npart: int, rows: int, q_temp, k_temp, v_temp, skip_head_norm: bool = False, loras=None) -> None:
         """skip_head_norm: a handle's q / k head norm is left to the attention launch (attn_decode_fused(head_norm=...))"""
+        if loras: raise RuntimeError("q_attn_forward_1_chain: adapters are not built for the chained decode kernels (take the module-by-module step)")
         self.lib.check(self.lib.exl2_q_attn_forward_1_chain_ex(
             q_attn, self._ptr(xp, torch.float16, "xp"), self._ptr(ss, torch.float32, "ss"), int(npart), int(rows),
             self._ptr(q_temp, torch.float16, "q_temp"), self._ptr(k_temp, torch.float16, "k_temp"),
             self._ptr(v_temp, torch.float16, "v_temp"), int(bool(skip_head_norm)), self._stream(xp)))
 
     def q_attn_forward_1_chain_rope(self, q_attn, xp, ss, npart: int, batch_size: int, q_len: int, past_len: int, past_lens,
-                                    q_temp, k_temp, v_temp, sin, cos) -> None:
+                                    q_temp, k_temp, v_temp, sin, cos, loras=None) -> None:
         """q_attn_forward_1's contract (projections, head norm, RoPE in place) from a published hand-off"""
+        if loras: raise RuntimeError("q_attn_forward_1_chain_rope: adapters are not built for the chained decode kernels (take the module-by-module step)")
         self.lib.check(self.lib.exl2_q_attn_forward_1_chain_rope(
             q_attn, self._ptr(xp, torch.float16, "xp"), self._ptr(ss, torch.float32, "ss"), int(npart), int(batch_size), int(q_len),
             int(past_len), self._ptr(past_lens, torch.int32, "past_lens"), self._ptr(q_temp, torch.float16, "q_temp"),
@@ -783,9 +857,10 @@ class ExtC:
         self.lib.check(self.lib.exl2_q_attn_head_norm_info(q_attn, C.byref(a), C.byref(b), C.byref(e), C.byref(r)))
         return a.value, b.value, float(e.value), bool(r.value)
 
-    def q_attn_forward_2_chain(self, q_attn, x, attn_out_packed, rows: int, next_invperm, next_norm_w, xp_out, ss_out) -> int:
+    def q_attn_forward_2_chain(self, q_attn, x, attn_out_packed, rows: int, next_invperm, next_norm_w, xp_out, ss_out, loras=None) -> int:
         """x += attn_out . Wo; publishes xp_out = x * next_norm_w in the next consumer's order + partial sums of x^2.
         Returns the number of partial sums per row written to ss_out."""
+        if loras: raise RuntimeError("q_attn_forward_2_chain: adapters are not built for the chained decode kernels (take the module-by-module step)")
         n = C.c_int(0)
         self.lib.check(self.lib.exl2_q_attn_forward_2_chain(
             q_attn, self._ptr(x, torch.float16, "x"), self._ptr(attn_out_packed, torch.float16, "attn_out"), int(rows),
@@ -793,7 +868,8 @@ class ExtC:
             self._ptr(ss_out, torch.float32, "ss_out"), C.byref(n), self._stream(x)))
         return n.value
 
-    def q_mlp_forward_chain(self, q_mlp, x, xp, ss, npart: int, rows: int, next_invperm, next_norm_w, xp_out, ss_out) -> int:
+    def q_mlp_forward_chain(self, q_mlp, x, xp, ss, npart: int, rows: int, next_invperm, next_norm_w, xp_out, ss_out, loras=None) -> int:
+        if loras: raise RuntimeError("q_mlp_forward_chain: adapters are not built for the chained decode kernels (take the module-by-module step)")
         n = C.c_int(0)
         self.lib.check(self.lib.exl2_q_mlp_forward_chain(
             q_mlp, self._ptr(x, torch.float16, "x"), self._ptr(xp, torch.float16, "xp"), self._ptr(ss, torch.float32, "ss"),
@@ -802,9 +878,10 @@ class ExtC:
         return n.value
 
     def q_mlp_forward_chain_part(self, q_mlp, part: int, row0: int, x, xp, ss, npart: int, rows: int, next_invperm, next_norm_w,
-                                 xp_out, ss_out) -> int:
+                                 xp_out, ss_out, loras=None) -> int:
         """one half of q_mlp_forward_chain for rows [row0, row0 + rows) (tensors are the row-group slices): part 1 = gate | up,
         part 2 = down (returns the partial sums per row it published)"""
+        if loras: raise RuntimeError("q_mlp_forward_chain_part: adapters are not built for the chained decode kernels (take the module-by-module step)")
         n = C.c_int(0)
         self.lib.check(self.lib.exl2_q_mlp_forward_chain_part(
             q_mlp, int(part), int(row0), self._ptr(x, torch.float16, "x"), self._ptr(xp, torch.float16, "xp"),
@@ -812,8 +889,9 @@ class ExtC:
             self._ptr(xp_out, torch.float16, "xp_out"), self._ptr(ss_out, torch.float32, "ss_out"), C.byref(n), self._stream(x)))
         return n.value
 
-    def q_moe_mlp_forward_chain(self, q_moe, x, rows: int, next_invperm, next_norm_w, xp_out, ss_out) -> int:
+    def q_moe_mlp_forward_chain(self, q_moe, x, rows: int, next_invperm, next_norm_w, xp_out, ss_out, loras=None) -> int:
         """q_moe_mlp_forward_ in place on x + the hand-off for the next consumer; returns the partial sums per row it published"""
+        if loras: raise RuntimeError("q_moe_mlp_forward_chain: adapters are not built for the chained decode kernels (take the module-by-module step)")
         n = C.c_int(0)
         self.lib.check(self.lib.exl2_q_moe_mlp_forward_chain(
             q_moe, self._ptr(x, torch.float16, "x"), int(rows), next_invperm or None, self._w_ptr(next_norm_w),

@@ -20,6 +20,8 @@ class ExLlamaV2Linear:
         self.padding = -out_features % 32                     # linear.py:82-88
         self.q_handle = None
         self.q_tensors = None
+        self.lora_a_tensors = {}                              # ExLlamaV2Lora -> fp16 [in_features, r]   (linear.py:62-63; filled by
+        self.lora_b_tensors = {}                              # ExLlamaV2Lora -> fp16 [r, out_features]   exllamav2_amd/lora.py)
 
     def load(self, w: dict, temp_dq=None, prescale: float = 1.0):
         """linear.py:118-171: keep the tensors alive (the handle stores raw pointers) and build the handle."""
@@ -33,6 +35,12 @@ class ExLlamaV2Linear:
             self.ext.free_q_matrix(self.q_handle)             # linear.py:236-239
             self.q_handle = None
         self.q_tensors = None
+        self.lora_a_tensors, self.lora_b_tensors = {}, {}
+
+    def lora_table(self) -> dict:
+        """{id(lora): (A, B, rank)} of the adapters that carry both halves for this layer: the dict q_attn_set_loras / q_mlp_set_loras
+        take (attn.py:1545-1566)"""
+        return {id(l): (a, self.lora_b_tensors[l], a.shape[1]) for l, a in self.lora_a_tensors.items() if l in self.lora_b_tensors}
 
     def forward(self, hidden_states: torch.Tensor, force_recons: bool = False, force_cuda: bool = False) -> torch.Tensor:
         """linear.py:361-379: gemm_half_q_half; reconstruct + torch.matmul ONLY when the caller asks for it (force_recons,

@@ -34,8 +34,12 @@ class ExLlamaV2MLP:
         for lin in (self.gate_proj, self.up_proj, self.down_proj):
             lin.unload()
 
-    def forward(self, hidden_states: torch.Tensor):
+    def update_loras(self) -> int:
+        """mlp.py:525-544: hands the adapters attached to the three linears to the handle; returns the largest rank"""
+        return self.ext.q_mlp_set_loras(self.q_handle, self.gate_proj.lora_table(), self.up_proj.lora_table(), self.down_proj.lora_table())
+
+    def forward(self, hidden_states: torch.Tensor, loras=None):
         """mlp.py:353: ext_c.q_mlp_forward_ in place, for every row count (<= 16 rows: the fused decode launches; above:
-        row pre-pass + dequantize-into-MFMA GEMMs, csrc/modules.hip:exl2_q_mlp_forward)."""
-        self.ext.q_mlp_forward_(self.q_handle, hidden_states)
+        row pre-pass + dequantize-into-MFMA GEMMs, csrc/modules.hip:exl2_q_mlp_forward).  loras: the ExLlamaV2Lora adapters to apply."""
+        self.ext.q_mlp_forward_(self.q_handle, hidden_states, loras=[id(l) for l in loras] if loras else None)
         return hidden_states

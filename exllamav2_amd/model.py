@@ -106,6 +106,21 @@ class ExLlamaV2:
             if ExLlamaV2._live_on_device[k] == 0:
                 self.ext.release_scratch(self.device)
 
+    def linear_modules(self) -> dict:
+        """key -> ExLlamaV2Linear of the layers' dense projections (what a LoRA adapter may target: exllamav2_amd/lora.py)"""
+        out = {}
+        for attn, mlp in self.layers:
+            lins = [attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj]
+            if hasattr(mlp, "gate_proj"):
+                lins += [mlp.gate_proj, mlp.up_proj, mlp.down_proj]
+            out.update({lin.key: lin for lin in lins})
+        return out
+
+    def update_loras(self) -> int:
+        """model.py:355-364: every module rebuilds its adapter table from what is attached to its linears.  Graphs captured with the
+        previous tables must not be replayed afterwards.  Returns the largest rank."""
+        return max([m.update_loras() for m in self.modules if hasattr(m, "update_loras")] + [0])
+
     def weight_bytes(self) -> int:
         """Algorithmic bytes one token streams through the linears.  A sparse-MoE layer streams
         its router plus `num_experts_per_token` of its experts per token (moe_mlp.py:238-253)."""
@@ -123,13 +138,18 @@ class ExLlamaV2:
     # ---- forward ------------------------------------------------------------------------------------------------------
 
     def forward_chunk(self, input_ids: torch.Tensor, cache, past_len: int = 0, cache_seqlens=None, block_table=None,
-                      last_id_only: bool = True, preprocess_only: bool = False):
-        """model.py:936-1054.  input_ids [b, q_len] (any device); returns logits [b, q_len | 1, vocab] or None."""
+                      last_id_only: bool = True, preprocess_only: bool = False, loras=None):
+        """model.py:936-1054.  input_ids [b, q_len] (any device); returns logits [b, q_len | 1, vocab] or None.
+        loras: the ExLlamaV2Lora adapters to apply in every layer (None / empty: the plain launches)."""
         cfg = self.config
         b, q_len = input_ids.shape
         assert b * q_len <= self.max_rows, "chunk larger than the scratch arena"
         x = self.embed_tokens[input_ids.to(self.device).reshape(-1)].view(b, q_len, cfg.hidden_size).contiguous()
         for attn, mlp in self.layers:
+            if loras:
+                attn.forward(x, cache, past_len, cache_seqlens, block_table, loras=loras)
+                mlp.forward(x, loras=loras)
+                continue
             attn.forward(x, cache, past_len, cache_seqlens, block_table)
             mlp.forward(x)
         if preprocess_only:
@@ -141,7 +161,7 @@ class ExLlamaV2:
         return logits[..., :cfg.vocab_size]
 
     def forward(self, input_ids: torch.Tensor, cache, last_id_only: bool = True, preprocess_only: bool = False,
-                input_mask=None):
+                input_mask=None, loras=None):
         """model.py:764-933: contiguous-cache forward with chunked prefill; advances cache.current_seq_len."""
         b, q_len = input_ids.shape
         chunk = max(1, self.max_rows // b)                    # model.py:833 effective_max_input_len
@@ -153,7 +173,8 @@ class ExLlamaV2:
             n = min(chunk, q_len - pos)
             last = pos + n == q_len
             r = self.forward_chunk(input_ids[:, pos:pos + n], cache, past + pos,
-                                   last_id_only=last_id_only, preprocess_only=preprocess_only or (last_id_only and not last))
+                                   last_id_only=last_id_only, preprocess_only=preprocess_only or (last_id_only and not last),
+                                   loras=loras)
             if r is not None:
                 out = r if (out is None or last_id_only) else torch.cat([out, r], dim=1)
             pos += n
@@ -202,8 +223,11 @@ class GreedyGraphDecoder:
     graph.  Procedure = test_inference.py:604-609 (forward(ids[:, -1:], cache); argmax; append) with the token feedback
     and the position counters kept on the device, so a token costs one graph launch and no host synchronisation."""
 
-    def __init__(self, model: ExLlamaV2, cache, batch_size: int = 1, max_new_tokens: int = 4096):
+    def __init__(self, model: ExLlamaV2, cache, batch_size: int = 1, max_new_tokens: int = 4096, loras=None):
+        """loras: ExLlamaV2Lora adapters every step applies.  Such a decoder takes the module-by-module step (the chained decode
+        kernels carry no adapters), still one captured graph per token."""
         self.model, self.cache, self.b = model, cache, batch_size
+        self.loras = list(loras) if loras else None
         cfg, dev = model.config, model.device
         pages_per_seq = cache.max_seq_len // PAGE_SIZE
         assert cache.max_seq_len % PAGE_SIZE == 0
@@ -222,7 +246,7 @@ class GreedyGraphDecoder:
         self.chain = None
         self.pos = 0                  # host mirror of cache_seqlens (all rows advance together): bounds are checked here,
         self.limit = min(cache.max_seq_len, cfg.max_seq_len)      # the kernels index pages / sin-cos rows unchecked
-        if os.environ.get("EXL2_CHAIN", "1") != "0":
+        if os.environ.get("EXL2_CHAIN", "1") != "0" and not self.loras:
             self._setup_chain()
         if os.environ.get("EXL2_CHAIN_OVERLAP", "0") != "0" and (self.chain is None or "flags" not in self.chain):
             raise RuntimeError("EXL2_CHAIN_OVERLAP=1 asked for the experimental overlapped chain, but this model / cache / batch is "
@@ -470,6 +494,10 @@ class GreedyGraphDecoder:
         m, ext, cfg = self.model, self.model.ext, self.model.config
         ext.embed_rows(m.embed_tokens, self.ids, self.x.view(self.b, cfg.hidden_size))
         for attn, mlp in m.layers:
+            if self.loras:
+                attn.forward(self.x, self.cache, 0, self.cache_seqlens, self.block_table, loras=self.loras)
+                mlp.forward(self.x, loras=self.loras)
+                continue
             attn.forward(self.x, self.cache, 0, self.cache_seqlens, self.block_table)
             mlp.forward(self.x)
         ext.rms_norm(self.x.view(self.b, -1), m.norm.weight, self.xn.view(self.b, -1), cfg.norm_eps)

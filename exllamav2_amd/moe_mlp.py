@@ -45,8 +45,9 @@ class ExLlamaV2MoEMLP:
         for lin in self.w1 + self.w2 + self.w3:
             lin.unload()
 
-    def forward(self, hidden_states: torch.Tensor):
-        """moe_mlp.py:238-253: ext_c.q_moe_mlp_forward_ in place (x += sum_e w_e * down_e(act(gate_e n) * up_e n))."""
+    def forward(self, hidden_states: torch.Tensor, loras=None):
+        """moe_mlp.py:238-253: ext_c.q_moe_mlp_forward_ in place (x += sum_e w_e * down_e(act(gate_e n) * up_e n)).
+        loras: refused when not empty (adapters on the experts are not built; the reference's are commented out, q_mlp.cu:404-436)."""
         h = hidden_states.shape[-1]
-        self.ext.q_moe_mlp_forward_(self.q_handle, hidden_states.view(-1, h))
+        self.ext.q_moe_mlp_forward_(self.q_handle, hidden_states.view(-1, h), loras=[id(l) for l in loras] if loras else None)
         return hidden_states

@@ -41,7 +41,9 @@ class PipelineStage:
     """One rank's slice of the model + per-sequence decode state (device-side positions, like GreedyGraphDecoder)."""
 
     def __init__(self, cfg, rank: int, world: int, device, n_seqs: int, max_seq_len: int, recipe: str = "4.0bpw",
-                 seed: int = 0, ext=None, use_graph: bool = True, cache_type: str = "fp16", depth: int = 1):
+                 seed: int = 0, ext=None, use_graph: bool = True, cache_type: str = "fp16", depth: int = 1, loras=None):
+        if loras:
+            raise RuntimeError("pipeline stage: LoRA adapters are not built for the layer split yet")
         assert depth in (1, 2) and (depth == 1 or n_seqs % 2 == 0), "depth 2 needs an even number of sequences"
         self.cfg, self.rank, self.world, self.n_seqs, self.depth = cfg, rank, world, n_seqs, depth
         self.first, self.last = rank == 0, rank == world - 1

@@ -338,6 +338,17 @@ class ExLlamaV2TP(ExLlamaV2):
         super().__init__(local, device=device, ext=ext)
         # the prefill policy route (reconstruct + library GEMM) works per shard as it does per matrix
 
+    def linear_modules(self) -> dict:
+        raise RuntimeError("tensor parallel: LoRA adapters are not built for the split modules yet")
+
+    def update_loras(self) -> int:
+        raise RuntimeError("tensor parallel: LoRA adapters are not built for the split modules yet")
+
+    def forward_chunk(self, *args, loras=None, **kw):
+        if loras:
+            raise RuntimeError("tensor parallel: LoRA adapters are not built for the split modules yet")
+        return super().forward_chunk(*args, **kw)
+
     def load(self, ck: dict, layers=None):
         """`ck` holds FULL tensors (every rank reads the same checkpoint, like the reference's loader); each module
         keeps only its column shards."""
@@ -382,7 +393,9 @@ class TPGreedyDecoder:
     same step on its shards and ends up with the same token (the logits are gathered, argmax is deterministic), so no
     token broadcast is needed.  Positions and token feedback live on the device, like GreedyGraphDecoder."""
 
-    def __init__(self, model: ExLlamaV2TP, cache, batch_size: int = 1):
+    def __init__(self, model: ExLlamaV2TP, cache, batch_size: int = 1, loras=None):
+        if loras:
+            raise RuntimeError("tensor parallel: LoRA adapters are not built for the split modules yet")
         from .cache import PAGE_SIZE
         self.model, self.cache, self.b = model, cache, batch_size
         cfg, dev = model.full_config, model.device

@@ -316,6 +316,37 @@ int exl2_make_q_mlp(void** handle, const void* layernorm, const void* layernorm_
 int exl2_free_q_mlp(void* handle);
 int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream);
 
+/* ---- LoRA adapters (csrc/lora.hip; replaces apply_loras_cuda, cuda/lora.cu:5-34) ---------------------------------------------------
+   out[rows, N] += sum over the listed adapters l of fp16(x[rows, K] A_l[K, r_l]) B_l[r_l, N]: fp32 accumulation on the matrix
+   cores, the low-rank intermediate rounded to fp16 once (the reference's `temp`), the sum over the adapters plus the value in `out`
+   rounded once.  A [K, r] and B [r, N] are fp16, row-major (what lora.py:164-168 leaves: transposed, B pre-scaled); 1 <= r <= 256;
+   K and N multiples of 32.  A listed id the table does not hold, and an adapter without an entry for a projection, are skipped
+   (lora.cu:20-21); more than 8 listed adapters of the table in one call are refused.  At most two launches per group and call, no
+   allocation, no synchronisation: the launches can be captured in a graph.
+   q_attn_set_loras (ext_qattn.cpp:193-254) / q_mlp_set_loras (ext_qmlp.cpp:120-169): REPLACE the handle's adapter table with n_loras
+   adapters; a / b / ranks hold n_loras * 4 (q, k, v, o) resp. n_loras * 3 (gate, up, down) entries, adapter-major; a null pointer or
+   rank 0 = no entry.  The handle keeps its own copies (the caller's tensors may go away) and the scratch of the launches; load-time
+   calls: they synchronise, and no captured graph that ran the previous table may be replayed afterwards.  Return the largest rank. */
+int exl2_q_attn_set_loras(void* handle, int n_loras, const uint64_t* ids, const void* const* a, const void* const* b, const int* ranks);
+int exl2_q_mlp_set_loras(void* handle, int n_loras, const uint64_t* ids, const void* const* a, const void* const* b, const int* ranks);
+/* q_attn_forward_1 / q_attn_forward_2 / q_mlp_forward_ with their `loras` list (ext_qattn.cpp:115-191, ext_qmlp.cpp:87-118).  n_loras
+   == 0: the entry points above, launch for launch.  Otherwise the reference's unfused sequence, so that the rows the adapters read
+   exist in memory (q_attn.cu:266-283,344; q_mlp.cu:176-235): norm into temp_state, the projections from it, the adapters of the group
+   (q | k | v; gate | up) in one launch pair, act * up in place, o_proj / down_proj and their adapters on x. */
+int exl2_q_attn_forward_1_loras(void* handle, const void* x, int batch_size, int q_len, int past_len, const int* past_lens,
+                                void* temp_q, void* temp_k, void* temp_v, const void* sin, const void* cos, int apply_rope,
+                                int n_loras, const uint64_t* lora_ids, void* stream);
+int exl2_q_attn_forward_2_loras(void* handle, void* x, const void* attn_output, int batch_size, int q_len, int n_loras,
+                                const uint64_t* lora_ids, void* stream);
+int exl2_q_mlp_forward_loras(void* handle, void* x, int rows, int n_loras, const uint64_t* lora_ids, void* stream);
+/* A group of 1 .. 3 projections [in_features, out_features[p]] that read the same rows, on its own (the modules own theirs):
+   apply_loras_cuda (lora.cu:5-34) for every projection of the group in one launch pair.  exl2_lora_group_set_loras: as the setters
+   above with n_loras * n_proj entries.  exl2_apply_loras: x [rows, in_features], out[p] [rows, out_features[p]], rows <= max_rows. */
+int exl2_make_lora_group(void** handle, int n_proj, int in_features, const int* out_features, int max_rows);
+int exl2_free_lora_group(void* handle);
+int exl2_lora_group_set_loras(void* handle, int n_loras, const uint64_t* ids, const void* const* a, const void* const* b, const int* ranks);
+int exl2_apply_loras(void* handle, int n_loras, const uint64_t* ids, const void* x, void* const* out, int rows, void* stream);
+
 /* make_q_moe_mlp / q_moe_mlp_forward_ (ext_qmlp.h, ext_qmlp.cpp:245-272 -> QMoEMLP::forward_ cuda/q_mlp.cu:318-402).
    w1 / w2 / w3: arrays of num_experts q_matrix handles (gate, down, up projections).  num_experts in {4, 8, 16}.
    The reference accepts rows <= 4; this entry point takes any rows <= max_rows (16-row passes). */
