@@ -63,6 +63,8 @@ struct Api
     int (*q_attn_forward_1_loras)(void*, cvp, int, int, int, const int*, void*, void*, void*, cvp, cvp, int, int, const uint64_t*, void*);
     int (*q_attn_forward_2_loras)(void*, void*, cvp, int, int, int, const uint64_t*, void*);
     int (*q_mlp_forward_loras)(void*, void*, int, int, const uint64_t*, void*);
+    int (*q_attn_residual_fp32)(void*);
+    int (*q_mlp_residual_fp32)(void*);
 };
 Api api;
 void* dll = nullptr;
@@ -128,6 +130,7 @@ struct State
     std::unordered_set<void*> blocked;
     long long n_mismatch = 0; bool warned = false;
     std::unordered_map<void*, ModInfo> info;
+    std::unordered_map<void*, bool> fp32;       // module handle -> made with residual_fp32 (Gemma-2 / Gemma-3: x is fp32)
     std::unordered_map<void*, void*> succ;
     std::unordered_map<int, DevBuf> bufs;
     // the module that finished last, and on which residual tensor
@@ -274,12 +277,34 @@ void init(const std::string& path, bool cpu_ok)
     bind(api.q_attn_forward_1_loras, "exl2_q_attn_forward_1_loras");
     bind(api.q_attn_forward_2_loras, "exl2_q_attn_forward_2_loras");
     bind(api.q_mlp_forward_loras, "exl2_q_mlp_forward_loras");
+    bind(api.q_attn_residual_fp32, "exl2_q_attn_residual_fp32");
+    bind(api.q_mlp_residual_fp32, "exl2_q_mlp_residual_fp32");
     S = State();
     if (const char* e = getenv("EXL2_MODULE_CHAIN")) S.on = atoi(e) != 0;
     if (const char* e = getenv("EXL2_MODULE_CHAIN_VERIFY")) S.verify = atoi(e) != 0;
     if (const char* e = getenv("EXL2_MODULE_CHAIN_VERIFY_FIRST")) S.verify_first = atoi(e) < 0 ? 0 : atoi(e);
     if (const char* e = getenv("EXL2_MODULE_CHAIN_VERIFY_EVERY")) S.verify_every = atoi(e) < 0 ? 0 : atoi(e);
     if (const char* e = getenv("EXL2_MODULE_CHAIN_ROWS")) { const int v = atoi(e); if (v >= 1 && v <= 16) S.max_rows = v; }
+}
+
+// The residual tensor of a module call: its dtype has to match the handle's (ext_qattn.cpp:133-134).  fp32 = the handle has an fp32
+// residual stream: the call goes to the plain C entry point, which takes x as fp32, and the module chain never engages for it.
+void* residual_ptr(void* h, bool attn, const at::Tensor& x, bool& fp32)
+{
+    auto it = S.fp32.find(h);
+    if (it == S.fp32.end())
+    {
+        const int rc = attn ? api.q_attn_residual_fp32(h) : api.q_mlp_residual_fp32(h);
+        if (rc < 0) check(rc);
+        it = S.fp32.emplace(h, rc == 1).first;
+    }
+    fp32 = it->second;
+    if (!fp32) return f16_ptr(x, "x");
+    if (!x.defined() || x.is_meta()) return nullptr;
+    if (x.scalar_type() != at::kFloat) throw std::runtime_error("x: expected dtype torch.float32 (the module has an fp32 residual stream)");
+    if (!x.is_contiguous()) throw std::runtime_error("x: tensor must be contiguous");
+    if (!x.is_cuda() && !(allow_cpu && x.is_cpu())) throw std::runtime_error("x: tensor must live on a HIP device; there is no CPU path");
+    return x.data_ptr();
 }
 
 void q_attn_forward_1(uintptr_t handle, const at::Tensor& x, int batch_size, int q_len, int past_len, const at::Tensor& past_lens,
@@ -291,7 +316,8 @@ void q_attn_forward_1(uintptr_t handle, const at::Tensor& x, int batch_size, int
     void* h = (void*)handle;
     c10::OptionalDeviceGuard guard; if (x.is_cuda()) guard.reset_device(x.device());
     void* stream = stream_of(x);
-    void* xq = f16_ptr(x, "x");
+    bool fp32 = false;
+    void* xq = residual_ptr(h, true, x, fp32);
     void* q = f16_ptr(q_temp, "q_temp"); void* k = f16_ptr(k_temp, "k_temp"); void* v = f16_ptr(v_temp, "v_temp");
     const int rows = batch_size * q_len;
     const int hidden = (int)x.size(-1);
@@ -305,7 +331,7 @@ void q_attn_forward_1(uintptr_t handle, const at::Tensor& x, int batch_size, int
                                          (int)ids.size(), ids.data(), stream));
         return;
     }
-    if (chain_rows(rows))
+    if (!fp32 && chain_rows(rows))
     {
         ModInfo& mi = info_of(h, true);
         if (mi.capable && rows <= mi.rows_ok)
@@ -428,7 +454,8 @@ void q_attn_forward_2(uintptr_t handle, const at::Tensor& x, const at::Tensor& a
     void* h = (void*)handle;
     c10::OptionalDeviceGuard guard; if (x.is_cuda()) guard.reset_device(x.device());
     void* stream = stream_of(x);
-    void* xq = f16_ptr(x, "x"); void* ao = f16_ptr(attn_output, "attn_output");
+    bool fp32 = false;
+    void* xq = residual_ptr(h, true, x, fp32); void* ao = f16_ptr(attn_output, "attn_output");
     const int rows = batch_size * q_len;
     const int hidden = (int)x.size(-1);
     if (!ids.empty())
@@ -438,7 +465,7 @@ void q_attn_forward_2(uintptr_t handle, const at::Tensor& x, const at::Tensor& a
         check(api.q_attn_forward_2_loras(h, xq, ao, batch_size, q_len, (int)ids.size(), ids.data(), stream));
         return;
     }
-    if (chain_rows(rows) && S.packed_for == h && S.attn_out.is(attn_output, rows, stream))
+    if (!fp32 && chain_rows(rows) && S.packed_for == h && S.attn_out.is(attn_output, rows, stream))
     {
         const Publish p = successor(h, x, hidden);
         int npart = 0;
@@ -456,7 +483,7 @@ void q_attn_forward_2(uintptr_t handle, const at::Tensor& x, const at::Tensor& a
     S.n_plain++;
     check(api.q_attn_forward_2(h, xq, ao, batch_size, q_len, stream));
     // (the order is still learnt: the next module publishes its own hand-off)
-    if (chain_rows(rows)) { Publish none{nullptr, nullptr, nullptr, nullptr, nullptr, 0}; finished(h, x, rows, stream, none, 0); }
+    if (!fp32 && chain_rows(rows)) { Publish none{nullptr, nullptr, nullptr, nullptr, nullptr, 0}; finished(h, x, rows, stream, none, 0); }
     else drop_all();
 }
 
@@ -467,7 +494,8 @@ void q_mlp_forward_(uintptr_t handle, const at::Tensor& x, const py::object& lor
     void* h = (void*)handle;
     c10::OptionalDeviceGuard guard; if (x.is_cuda()) guard.reset_device(x.device());
     void* stream = stream_of(x);
-    void* xq = f16_ptr(x, "x");
+    bool fp32 = false;
+    void* xq = residual_ptr(h, false, x, fp32);
     const int hidden = (int)x.size(-1);
     const int rows = (int)(x.numel() / hidden);
     if (!ids.empty())
@@ -477,7 +505,7 @@ void q_mlp_forward_(uintptr_t handle, const at::Tensor& x, const py::object& lor
         check(api.q_mlp_forward_loras(h, xq, rows, (int)ids.size(), ids.data(), stream));
         return;
     }
-    if (chain_rows(rows))
+    if (!fp32 && chain_rows(rows))
     {
         ModInfo& mi = info_of(h, false);
         if (mi.capable && rows <= mi.rows_ok)
@@ -513,7 +541,7 @@ void forget_module(uintptr_t handle)
 {
     LOCKED;
     void* h = (void*)handle;
-    S.info.erase(h); S.succ.erase(h); S.edge_uses.erase(h); S.blocked.erase(h);
+    S.info.erase(h); S.succ.erase(h); S.edge_uses.erase(h); S.blocked.erase(h); S.fp32.erase(h);
     for (auto it = S.succ.begin(); it != S.succ.end();) { if (it->second == h) it = S.succ.erase(it); else ++it; }
     drop_all();
 }
@@ -533,7 +561,7 @@ void set_chain(bool on) { S.on = on; drop_all(); }
 void set_verify(bool on) { S.verify = on; }
 void set_verify_sampling(int first, int every) { S.verify_first = first < 0 ? 0 : first; S.verify_every = every < 0 ? 0 : every; }
 void set_max_rows(int n) { if (n >= 1 && n <= 16) S.max_rows = n; drop_all(); }
-void reset() { drop_all(); S.succ.clear(); S.info.clear(); S.bufs.clear(); S.edge_uses.clear(); S.blocked.clear(); S.warned = false; }
+void reset() { drop_all(); S.succ.clear(); S.info.clear(); S.fp32.clear(); S.bufs.clear(); S.edge_uses.clear(); S.blocked.clear(); S.warned = false; }
 
 }  // namespace
 

@@ -135,6 +135,10 @@ if _fast is not None:
     def q_moe_mlp_forward_(q_moe_mlp, x, loras=None, loras_temp=None):
         _fast.note_write(x)
         return _e.q_moe_mlp_forward_(q_moe_mlp, x, loras, loras_temp)
+
+    def softcap_(x, scale):
+        _fast.note_write(x)
+        return _e.softcap_(x, scale)
 else:
     q_attn_forward_1 = _e.q_attn_forward_1
     q_attn_forward_2 = _e.q_attn_forward_2
@@ -148,6 +152,7 @@ else:
     head_norm_ = _e.head_norm_
     rope_ = _e.rope_
     q_moe_mlp_forward_ = _e.q_moe_mlp_forward_
+    softcap_ = _e.softcap_                   # ext_element.cpp:28-50 (csrc/gemma_ops.hip)
 
 
 def set_flash_attn_func():          # ext_qattn.cpp:256-259 is a no-op in the reference too
@@ -202,7 +207,7 @@ cache_rotate = _e.cache_rotate
 count_match = _e.count_match
 matrix_fp16_to_q4 = _e.matrix_fp16_to_q4
 matrix_q4_to_fp16 = _e.matrix_q4_to_fp16
-for _n in ("layer_norm", "layer_norm_", "softcap_", "gen_mrope_pos_ids", "gemm_half_half_half",
+for _n in ("layer_norm", "layer_norm_", "gen_mrope_pos_ids", "gemm_half_half_half",
            "had_paley", "had_paley2", "pack_rows_4", "pack_columns", "quantize", "quantize_err", "quantize_range",
            "quantize_range_inplace", "sim_anneal", "logit_filter_exclusive",
            "dump_profile_results", "stloader_open_file", "stloader_close_file"):

@@ -91,6 +91,15 @@ PROTOTYPES = {
     "exl2_make_q_mlp": (ci, [C.POINTER(vp), vp, vp, ci, cf, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, ci, ci]),
     "exl2_free_q_mlp": (ci, [vp]),
     "exl2_q_mlp_forward": (ci, [vp, vp, ci, vp]),
+    # fp32 residual stream: the forms for a caller that owns the norms (csrc/modules.hip), the bridge / cap / embedding (csrc/gemma_ops.hip)
+    "exl2_q_attn_forward_1_normed": (ci, [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]),
+    "exl2_q_attn_forward_2_normed": (ci, [vp, vp, ci, ci, vp]),
+    "exl2_q_mlp_forward_normed": (ci, [vp, vp, ci, vp]),
+    "exl2_q_attn_residual_fp32": (ci, [vp]),
+    "exl2_q_mlp_residual_fp32": (ci, [vp]),
+    "exl2_norm_bridge": (ci, [vp, vp, vp, vp, vp, cf, ci, ci, vp]),
+    "exl2_softcap": (ci, [vp, cll, cf, ci, vp]),
+    "exl2_embed_rows_f32": (ci, [vp, vp, vp, ci, ci, ci, cf, vp]),
     # LoRA adapters (csrc/lora.hip)
     "exl2_q_attn_set_loras": (ci, [vp, ci, vp, vp, vp, vp]),
     "exl2_q_mlp_set_loras": (ci, [vp, ci, vp, vp, vp, vp]),

@@ -46,18 +46,26 @@ class ExLlamaV2Attention:
         cfg, m = self.model.config, self.model
         for lin in (self.q_proj, self.k_proj, self.v_proj, self.o_proj):
             lin.load(ck[lin.key])
-        self.pre_layernorm = ck[self.key + ".input_layernorm"]
+        self.pre_layernorm = m.norm_weight(ck[self.key + ".input_layernorm"])
+        post = getattr(cfg, "post_norms", False)
+        self.post_layernorm = m.norm_weight(ck[self.key + ".post_attention_layernorm"]) if post else None
+        # per-layer sliding window and rotary table (model.py:111-121): window_left keys to the left, 0 = all
+        gi = int(self.key.rsplit(".", 1)[1])                                    # global layer index ("model.layers.N"); layer_idx is local
+        self.window = cfg.layer_window(gi)
+        self.sin, self.cos = (m.sin_alt, m.cos_alt) if cfg.layer_rope_alt(gi) else (m.sin, m.cos)
         if getattr(cfg, "use_qk_norm", False):                                  # attn.py:196-198, 285-289
-            self.q_norm = self._head_norm_weight(ck[self.key + ".self_attn.q_norm"], cfg.num_attention_heads, "q")
-            self.k_norm = self._head_norm_weight(ck[self.key + ".self_attn.k_norm"], cfg.num_key_value_heads, "k")
+            # (the constant bias of the architecture's norms goes to the head norms too: headnorm.py:78-79)
+            self.q_norm = self._head_norm_weight(m.norm_weight(ck[self.key + ".self_attn.q_norm"]), cfg.num_attention_heads, "q")
+            self.k_norm = self._head_norm_weight(m.norm_weight(ck[self.key + ".self_attn.k_norm"]), cfg.num_key_value_heads, "k")
         qn = none_tensor if self.q_norm is None else self.q_norm
         kn = none_tensor if self.k_norm is None else self.k_norm
         self.q_handle = self.ext.make_q_attn(                                   # attn.py:300-330
             self.pre_layernorm, none_tensor, True, bool(getattr(cfg, "headnorm_rms", True)), cfg.norm_eps,
             self.q_proj.q_handle, self.k_proj.q_handle, self.v_proj.q_handle, self.o_proj.q_handle,
             m.temp_state, none_tensor, m.max_rows, cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads,
-            cfg.head_dim, cfg.max_seq_len, True, cfg.rope_style, cfg.head_dim, qn, kn, none_tensor,
-            none_tensor, False, False)
+            cfg.head_dim, cfg.max_seq_len, True, cfg.rope_style, cfg.head_dim, qn, kn,
+            none_tensor if self.post_layernorm is None else self.post_layernorm,
+            none_tensor, bool(getattr(cfg, "residual_fp32", False)), False)
         return self
 
     def _head_norm_weight(self, w: torch.Tensor, heads: int, kind: str) -> torch.Tensor:
@@ -117,6 +125,26 @@ class ExLlamaV2Attention:
                              loras=lora_ids, apply_rope=False)
         return q, k, v
 
+    def forward_normed(self, xn: torch.Tensor, b: int, q_len: int, cache, past_len: int = 0, cache_seqlens=None, block_table=None):
+        """The module for a caller that owns the norms (a post-norm block): xn fp16 [b * q_len, hidden], already normed.  o_proj's output
+        is left in the model's temp_state; the post norm is the caller's (ext.norm_bridge)."""
+        cfg, m, ext = self.model.config, self.model, self.ext
+        rows = b * q_len
+        q = m.temp_q[:rows].view(b, q_len, cfg.num_attention_heads, cfg.head_dim)
+        k = m.temp_k[:rows].view(b, q_len, cfg.num_key_value_heads, cfg.head_dim)
+        v = m.temp_v[:rows].view(b, q_len, cfg.num_key_value_heads, cfg.head_dim)
+        ext.q_attn_forward_1_normed(self.q_handle, xn, b, q_len, 0, none_tensor, q, k, v, m.sin, m.cos, apply_rope=False)
+        attn_out = self._attend(q, k, v, cache, past_len, cache_seqlens, block_table)
+        ext.q_attn_forward_2_normed(self.q_handle, attn_out, b, q_len)
+
+    def attend_extras(self, cache):
+        """(window_left, softcap) when this layer's attention needs the launches that carry them -- a window that can clip inside this
+        cache, or a score cap -- else None: the one-launch decode attention (csrc/attn_fused_body.h) carries neither."""
+        cap = float(getattr(self.model.config, "attn_logit_softcapping", 0.0) or 0.0)
+        win = getattr(self, "window", 0)
+        clips = win > 0 and win + 1 < cache.max_seq_len
+        return (win if clips else -1, cap) if (clips or cap) else None
+
     def _attend(self, q, k, v, cache, past_len, cache_seqlens, block_table):
         """RoPE(q, new k) + KV append + attention over the (paged or contiguous, FP16 or Q4 / Q6 / Q8) cache -> attn_out rows."""
         cfg, m, ext = self.model.config, self.model, self.ext
@@ -130,6 +158,13 @@ class ExLlamaV2Attention:
         # range to an fp16 temp for every layer of every step (cache.py:472-514)
         # (the step's own K/V are attended in fp16 and quantised afterwards, the reference's order)
         wbits = getattr(cache, "wbits", 0)
+        scale = cfg.softmax_scale()
+        sin, cos = getattr(self, "sin", None), getattr(self, "cos", None)
+        if sin is None: sin, cos = m.sin, m.cos
+        extras = self.attend_extras(cache)
+        if wbits and (extras is not None or scale != cfg.head_dim ** -0.5 or sin is not m.sin):
+            raise RuntimeError(f"{self.key}: a quantized cache together with a sliding window, a score cap, a softmax scale or a rotary table "
+                               f"of the layer's own is not built (the kernels that attend from the codes carry none of them)")
         q4_direct = (wbits in (4, 6, 8) and hasattr(cache, "q4_views") and self.q4_fused and q_len <= 8
                      and q_len * (cfg.num_attention_heads // cfg.num_key_value_heads) <= 64
                      and cfg.head_dim in (64, 128, 256)
@@ -166,15 +201,19 @@ class ExLlamaV2Attention:
             if not ok:
                 raise RuntimeError("ExLlamaV2Attention: attention from the cache's codes rejected a shape it was selected for")
         else:
-            # decode-shaped steps: one launch does RoPE + append + attention + split merge; otherwise three launches
-            fused = self.fused_decode and ext.attn_decode_fused(
-                q, k, v, kc, vc, attn_out, m.sin, m.cos, sl, bt, past, cfg.rope_style, m.attn_scratch, m.attn_counters)
+            # decode-shaped steps: one launch does RoPE + append + attention + split merge; otherwise three launches.  A layer with a
+            # clipping window or a score cap always takes the three: rope_kv_append, then the attention launches that carry both
+            wl, cap = extras if extras is not None else (-1, 0.0)
+            fused = extras is None and self.fused_decode and ext.attn_decode_fused(
+                q, k, v, kc, vc, attn_out, sin, cos, sl, bt, past, cfg.rope_style, m.attn_scratch, m.attn_counters, softmax_scale=scale)
             if not fused:
-                ext.rope_kv_append(q, k, v, kc, vc, m.sin, m.cos, past if not paged else 0,
+                ext.rope_kv_append(q, k, v, kc, vc, sin, cos, past if not paged else 0,
                                    sl if paged else none_tensor, bt if paged else none_tensor, cfg.rope_style)
                 # many query rows: MFMA flash attention (csrc/attn_prefill.hip); decode-shaped: the split-KV kernel
-                if not (q_len > 16 and ext.flash_prefill(q, kc, vc, attn_out, sl, bt, len_const=past, len_offset=q_len)):
-                    ext.paged_attn(q, kc, vc, attn_out, sl, bt, len_const=past, len_offset=q_len, scratch=m.attn_scratch)
+                if not (q_len > 16 and ext.flash_prefill(q, kc, vc, attn_out, sl, bt, len_const=past, len_offset=q_len,
+                                                         softmax_scale=scale, window_left=wl, softcap=cap)):
+                    ext.paged_attn(q, kc, vc, attn_out, sl, bt, len_const=past, len_offset=q_len, softmax_scale=scale,
+                                   scratch=m.attn_scratch, window_left=wl, softcap=cap)
             if paged:
                 cache.store_kv_state(self.layer_idx, b, 0, q_len, 256, cache_seqlens, block_table)
             else:

@@ -24,6 +24,48 @@ class ExLlamaV2Config:
     num_experts_per_token: int = 2
     use_qk_norm: bool = False               # per-head norm of q / k between the projections and RoPE (architecture.py:446,459,609)
     headnorm_rms: bool = True               # its form: RMS (Qwen3, Gemma3, OLMo2) or LayerNorm over the head (Cohere)
+    # Gemma-2 / Gemma-3 blocks (architecture.py:554-613).  The defaults are every other family's.
+    residual_fp32: bool = False             # fp32 residual stream (residual_stream_fp32); such architectures have post norms (:955-957)
+    post_norms: bool = False                # .post_attention_layernorm / .post_feedforward_layernorm behind o_proj / down_proj,
+                                            # .pre_feedforward_layernorm ahead of the MLP (the "norm_1_post" / "norm_2" / "norm_2_post" keys)
+    norm_constant_bias: float = 0.0         # added to every RMSNorm weight in fp16 at load (rmsnorm.py:57-59)
+    normalize_embeddings: bool = False      # embedding rows times hidden_size ** 0.5, in fp32 (embedding.py:184-187)
+    mlp_act_func: str = "silu"              # "silu" | "gelu"
+    attn_logit_softcapping: float = 0.0     # cap * tanh(score / cap) on the scaled scores (attn.py:596-600); 0 = off
+    final_logit_softcapping: float = 0.0    # the same on the logits (model.py:1043-1044)
+    query_pre_attn_scalar: float = 0.0      # softmax scale = query_pre_attn_scalar ** -0.5 when set (attn.py:218-219)
+    sliding_window: int = 0                 # keys a windowed layer sees to the left (flash-attn's window_size[0], attn.py:595)
+    sliding_window_pattern: int = 1         # > 1: every pattern-th layer is global (Gemma-3: 6)
+    alternating_swa: bool = False           # windowed and global layers alternate (model.py:111-121)
+    rotary_embedding_base_alt: float = 0.0  # rope base of the windowed layers when they have their own (Gemma-3: 10000)
+
+    def __post_init__(self):
+        if self.mlp_act_func not in ("silu", "gelu"):
+            raise ValueError(f"mlp_act_func {self.mlp_act_func!r}: 'silu' or 'gelu'")
+        if self.residual_fp32 and not self.post_norms:
+            raise ValueError("residual_fp32 needs post_norms (the reference's check, architecture.py:955-957)")
+        if self.normalize_embeddings and not self.residual_fp32:
+            raise ValueError("normalize_embeddings without residual_fp32 (Gemma-1) is not built")
+        if self.post_norms and not self.residual_fp32:
+            raise ValueError("post_norms without residual_fp32 is not built in the native model")
+        if self.residual_fp32 and self.num_experts:
+            raise ValueError("a sparse-MoE MLP with an fp32 residual stream is not built")
+
+    def layer_window(self, layer_idx: int) -> int:
+        """Keys to the left a layer attends to, 0 = all (model.py:111-121): with alternating_swa, pattern > 1 windows the layers with
+        (idx + 1) % pattern != 0, pattern <= 1 the even ones."""
+        if not self.alternating_swa or self.sliding_window <= 0:
+            return 0
+        if self.sliding_window_pattern > 1:
+            return self.sliding_window if (layer_idx + 1) % self.sliding_window_pattern != 0 else 0
+        return self.sliding_window if layer_idx % 2 == 0 else 0
+
+    def layer_rope_alt(self, layer_idx: int) -> bool:
+        """the layer rotates with the second sin / cos table (rotary_embedding_base_alt): windowed layers of a pattern > 1 model"""
+        return bool(self.rotary_embedding_base_alt) and self.sliding_window_pattern > 1 and self.layer_window(layer_idx) > 0
+
+    def softmax_scale(self) -> float:
+        return float(self.query_pre_attn_scalar) ** -0.5 if self.query_pre_attn_scalar else float(self.head_dim) ** -0.5
 
     @staticmethod
     def llama2_7b(**kw):
@@ -60,6 +102,38 @@ class ExLlamaV2Config:
                  use_qk_norm=True, arch="qwen3")
         d.update(kw)
         return ExLlamaV2Config(**d)
+
+    @staticmethod
+    def _gemma2(**d):
+        base = dict(vocab_size=256000, max_seq_len=8192, norm_eps=1e-6, rotary_embedding_base=10000.0, arch="gemma2",
+                    residual_fp32=True, post_norms=True, norm_constant_bias=1.0, normalize_embeddings=True, mlp_act_func="gelu",
+                    attn_logit_softcapping=50.0, final_logit_softcapping=30.0, sliding_window=4096, alternating_swa=True)
+        base.update(d)
+        return ExLlamaV2Config(**base)
+
+    @staticmethod
+    def gemma2_2b(**kw):
+        return ExLlamaV2Config._gemma2(**(dict(hidden_size=2304, intermediate_size=9216, num_hidden_layers=26, num_attention_heads=8,
+                                               num_key_value_heads=4, head_dim=256, query_pre_attn_scalar=256.0) | kw))
+
+    @staticmethod
+    def gemma2_9b(**kw):
+        return ExLlamaV2Config._gemma2(**(dict(hidden_size=3584, intermediate_size=14336, num_hidden_layers=42, num_attention_heads=16,
+                                               num_key_value_heads=8, head_dim=256, query_pre_attn_scalar=256.0) | kw))
+
+    @staticmethod
+    def gemma2_27b(**kw):
+        return ExLlamaV2Config._gemma2(**(dict(hidden_size=4608, intermediate_size=36864, num_hidden_layers=46, num_attention_heads=32,
+                                               num_key_value_heads=16, head_dim=128, query_pre_attn_scalar=144.0) | kw))
+
+    @staticmethod
+    def gemma3_4b(**kw):
+        """the text model of Gemma-3 4B: q / k head norm, five windowed layers (their own rope base) per global one, no soft caps"""
+        return ExLlamaV2Config._gemma2(**(dict(hidden_size=2560, intermediate_size=10240, num_hidden_layers=34, num_attention_heads=8,
+                                               num_key_value_heads=4, head_dim=256, vocab_size=262208, query_pre_attn_scalar=256.0,
+                                               rotary_embedding_base=1e6, rotary_embedding_base_alt=10000.0, sliding_window=1024,
+                                               sliding_window_pattern=6, use_qk_norm=True, attn_logit_softcapping=0.0,
+                                               final_logit_softcapping=0.0, arch="gemma3") | kw))
 
     @staticmethod
     def tiny_test(**kw):

@@ -691,7 +691,10 @@ int exl2_make_q_attn(void** handle, const void* layernorm, const void* layernorm
     // the projections and RoPE (q_attn.cu:285-289) by every forward_1 below
     EXL2_REQUIRE(!q_norm == !k_norm, "make_q_attn: q_norm and k_norm come together");
     EXL2_REQUIRE(!q_norm || (head_dim % 8 == 0 && head_dim > 0 && head_dim <= 256), "make_q_attn: head norm needs head_dim %% 8 == 0 and <= 256 (got %d)", head_dim);
-    EXL2_REQUIRE(!residual_fp32, "make_q_attn: fp32 residual stream is not built");
+    // fp32 residual stream (Gemma-2 / Gemma-3): x is fp32, the pre-norm narrows it into temp_state and the post norm adds into it in fp32
+    // (q_attn.cu:268-279, :337-339); such architectures have post norms (architecture.py:955-957)
+    EXL2_REQUIRE(!residual_fp32 || (layernorm && layernorm_is_rms && post_layernorm),
+                 "make_q_attn: an fp32 residual stream needs an RMS pre-norm and a post norm");
     // (temp_state may be absent: the reference's tensor-parallel loader makes the handle without scratch, attn.py:259-272,
     // and never runs a forward on it; the forwards below refuse such a handle)
     QAttn* a = (QAttn*)calloc(1, sizeof(QAttn));
@@ -750,6 +753,33 @@ static int q_attn_head_norm(QAttn* a, int batch_size, int q_len, int past_len, c
                              q_len * a->num_heads, q_len * a->num_kv_heads, a->head_dim, a->num_heads, a->num_kv_heads, stream);
 }
 
+// q | k | v from rows that are already normed (fp16 [rows, hidden]: temp_state behind the pre-norm of an fp32 residual stream, or the
+// caller's own), then head norm / RoPE as every forward_1
+static int q_attn_qkv_normed(QAttn* a, const f16* ns, int batch_size, int q_len, int past_len, const int* past_lens,
+                             void* temp_q, void* temp_k, void* temp_v, const void* sin, const void* cos, int apply_rope,
+                             void* stream)
+{
+    const int rows = batch_size * q_len;
+    const bool gptq = a->q_proj->is_gptq;
+    EXL2_REQUIRE(a->k_proj->is_gptq == gptq && a->v_proj->is_gptq == gptq, "q_attn_forward_1: mixed EXL2/GPTQ projections");
+    EXL2_REQUIRE(!chain_sync_active(), "q_attn_forward_1: normed rows are not built for the overlapped chain");
+    GemvJob jobs[3];
+    fill_job(jobs[0], a->q_proj, ns, (f16*)temp_q, A_PLAIN, C_STORE);
+    fill_job(jobs[1], a->k_proj, ns, (f16*)temp_k, A_PLAIN, C_STORE);
+    fill_job(jobs[2], a->v_proj, ns, (f16*)temp_v, A_PLAIN, C_STORE);
+    jobs[1].rows_as_prev = jobs[2].rows_as_prev = a->qkv_same_perm ? 1 : 0;
+    LAUNCH_JOBS(jobs, 3, rows, gptq, stream, "q_attn_forward_1");
+    if (a->q_norm) return q_attn_head_norm(a, batch_size, q_len, past_len, past_lens, temp_q, temp_k, sin, cos, apply_rope, stream, "q_attn_forward_1");
+    if (apply_rope && a->rope_style != 0)
+    {
+        EXL2_REQUIRE(sin && cos, "q_attn_forward_1: sin/cos tables missing");
+        return exl2_rope_qk(temp_q, temp_k, sin, cos, batch_size, q_len * a->num_heads, q_len * a->num_kv_heads,
+                            a->head_dim, a->num_heads, a->num_kv_heads, past_len, past_lens, a->rope_style == 2,
+                            a->sincos_size, stream);
+    }
+    return EXL2_OK;
+}
+
 // q_attn_forward_1 (ext_qattn.cpp:115-159 -> q_attn.cu:247-317): q,k,v = proj(rmsnorm(x)); RoPE(q, k) in place.
 // apply_rope = 0 skips the rotation (the caller fuses it with the KV append, exl2_rope_kv_append).
 int exl2_q_attn_forward_1(void* handle, const void* x, int batch_size, int q_len, int past_len, const int* past_lens,
@@ -763,6 +793,13 @@ int exl2_q_attn_forward_1(void* handle, const void* x, int batch_size, int q_len
     EXL2_REQUIRE(a->temp_state || !a->layernorm, "q_attn_forward_1: handle was made without scratch (tensor-parallel load)");
     // temp_state (and the caller's temp_q/k/v) are sized for max_rows (attn.py:377-379 keeps chunks inside it)
     EXL2_REQUIRE(rows <= a->max_rows, "q_attn_forward_1: %d rows exceed max_rows %d", rows, a->max_rows);
+    if (a->residual_fp32)
+    {
+        // x is fp32: the pre-norm is a launch of its own, fp32 -> fp16 temp_state (q_attn.cu:268-279)
+        const int rc = exl2_rms_norm(x, a->layernorm, a->temp_state, a->norm_epsilon, rows, a->hidden_size, 0, 1, 0, stream);
+        if (rc) return rc;
+        return q_attn_qkv_normed(a, a->temp_state, batch_size, q_len, past_len, past_lens, temp_q, temp_k, temp_v, sin, cos, apply_rope, stream);
+    }
     const bool gptq = a->q_proj->is_gptq;
     EXL2_REQUIRE(a->k_proj->is_gptq == gptq && a->v_proj->is_gptq == gptq, "q_attn_forward_1: mixed EXL2/GPTQ projections");
     // RMSNorm rides in the staging of the rows for every row count: <= 16 rows in the decode kernel's prologue, above that in
@@ -804,8 +841,44 @@ int exl2_q_attn_forward_2(void* handle, void* x, const void* attn_output, int ba
     }
     fill_job(j, a->o_proj, (const f16*)attn_output, a->temp_state, A_PLAIN, C_STORE);
     LAUNCH_JOBS(&j, 1, rows, a->o_proj->is_gptq, stream, "q_attn_forward_2");
-    // add_residual is unconditional in the post-norm branch, as in the reference (q_attn.cu:339, q_mlp.cu:230)
-    return exl2_rms_norm(a->temp_state, a->post_layernorm, x, a->norm_epsilon, rows, a->hidden_size, 1, 0, 0, stream);
+    // add_residual is unconditional in the post-norm branch, as in the reference (q_attn.cu:339, q_mlp.cu:230); x fp32 for an fp32
+    // residual stream
+    return exl2_rms_norm(a->temp_state, a->post_layernorm, x, a->norm_epsilon, rows, a->hidden_size, 1, 0, a->residual_fp32 ? 1 : 0, stream);
+}
+
+// The attention module for a caller that owns the norms (include/exl2_hip.h): xn is the normed fp16 input, o_proj's output stays in
+// temp_state.
+int exl2_q_attn_forward_1_normed(void* handle, const void* xn, int batch_size, int q_len, int past_len, const int* past_lens,
+                                 void* temp_q, void* temp_k, void* temp_v, const void* sin, const void* cos, int apply_rope,
+                                 void* stream)
+{
+    EXL2_REQUIRE(handle && xn && temp_q && temp_k && temp_v, "q_attn_forward_1_normed: null argument");
+    QAttn* a = (QAttn*)handle;
+    const int rows = batch_size * q_len;
+    if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(rows <= a->max_rows, "q_attn_forward_1_normed: %d rows exceed max_rows %d", rows, a->max_rows);
+    return q_attn_qkv_normed(a, (const f16*)xn, batch_size, q_len, past_len, past_lens, temp_q, temp_k, temp_v, sin, cos, apply_rope, stream);
+}
+
+int exl2_q_attn_forward_2_normed(void* handle, const void* attn_output, int batch_size, int q_len, void* stream)
+{
+    EXL2_REQUIRE(handle && attn_output, "q_attn_forward_2_normed: null argument");
+    QAttn* a = (QAttn*)handle;
+    const int rows = batch_size * q_len;
+    if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(rows <= a->max_rows, "q_attn_forward_2_normed: %d rows exceed max_rows %d", rows, a->max_rows);
+    EXL2_REQUIRE(a->post_layernorm && a->temp_state, "q_attn_forward_2_normed: the handle needs a post norm and its scratch");
+    EXL2_REQUIRE(!chain_sync_active(), "q_attn_forward_2_normed: not built for the overlapped chain");
+    GemvJob j;
+    fill_job(j, a->o_proj, (const f16*)attn_output, a->temp_state, A_PLAIN, C_STORE);
+    LAUNCH_JOBS(&j, 1, rows, a->o_proj->is_gptq, stream, "q_attn_forward_2_normed");
+    return EXL2_OK;
+}
+
+int exl2_q_attn_residual_fp32(void* handle)
+{
+    EXL2_REQUIRE(handle, "q_attn_residual_fp32: null argument");
+    return ((QAttn*)handle)->residual_fp32 ? 1 : 0;
 }
 
 // q_attn_set_loras (ext_qattn.cpp:213-251): replaces the handle's adapter table.  a / b / ranks [n_loras * 4], adapter-major, in the
@@ -814,6 +887,8 @@ int exl2_q_attn_set_loras(void* handle, int n_loras, const uint64_t* ids, const 
 {
     EXL2_REQUIRE(handle && n_loras >= 0 && (n_loras == 0 || (ids && a && b && ranks)), "q_attn_set_loras: null argument");
     QAttn* at = (QAttn*)handle;
+    // (the reference adds adapter output into `(half*) hidden_state`, q_attn.cu:344: wrong for an fp32 x)
+    EXL2_REQUIRE(!at->residual_fp32, "q_attn_set_loras: adapters are not built for an fp32 residual stream");
     EXL2_REQUIRE(at->temp_state || !at->layernorm, "q_attn_set_loras: handle was made without scratch (tensor-parallel load)");
     if (!at->lora_qkv)
     {
@@ -854,6 +929,7 @@ int exl2_q_attn_forward_1_loras(void* handle, const void* x, int batch_size, int
     QAttn* a = (QAttn*)handle;
     const int rows = batch_size * q_len;
     if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(!a->residual_fp32, "q_attn_forward_1: adapters are not built for an fp32 residual stream");
     EXL2_REQUIRE(a->temp_state || !a->layernorm, "q_attn_forward_1: handle was made without scratch (tensor-parallel load)");
     EXL2_REQUIRE(rows <= a->max_rows, "q_attn_forward_1: %d rows exceed max_rows %d", rows, a->max_rows);
     const bool gptq = a->q_proj->is_gptq;
@@ -892,6 +968,7 @@ int exl2_q_attn_forward_1_loras(void* handle, const void* x, int batch_size, int
 int exl2_q_attn_forward_2_loras(void* handle, void* x, const void* attn_output, int batch_size, int q_len, int n_loras,
                                 const uint64_t* lora_ids, void* stream)
 {
+    EXL2_REQUIRE(n_loras <= 0 || !handle || !((QAttn*)handle)->residual_fp32, "q_attn_forward_2: adapters are not built for an fp32 residual stream");
     const int rc = exl2_q_attn_forward_2(handle, x, attn_output, batch_size, q_len, stream);
     if (rc || n_loras <= 0 || batch_size * q_len <= 0) return rc;
     EXL2_REQUIRE(lora_ids, "q_attn_forward_2: null argument");
@@ -909,7 +986,9 @@ int exl2_make_q_mlp(void** handle, const void* layernorm, const void* layernorm_
 {
     EXL2_REQUIRE(handle && q_up && q_down, "make_q_mlp: null projection handle");
     EXL2_REQUIRE(!layernorm || layernorm_is_rms, "make_q_mlp: only RMSNorm pre-norm is built (LayerNorm archs out of scope)");
-    EXL2_REQUIRE(!residual_fp32, "make_q_mlp: fp32 residual stream is not built");
+    // fp32 residual stream: as make_q_attn (q_mlp.cu:183, :230)
+    EXL2_REQUIRE(!residual_fp32 || (layernorm && layernorm_is_rms && post_layernorm),
+                 "make_q_mlp: an fp32 residual stream needs an RMS pre-norm and a post norm");
     // (scratch may be absent -- tensor-parallel load, mlp.py:169-190: the forwards refuse such a handle)
     QMLP* m = (QMLP*)calloc(1, sizeof(QMLP));
     if (!m) EXL2_FAIL(EXL2_E_OOM, "make_q_mlp: host out of memory");
@@ -942,28 +1021,17 @@ int exl2_free_q_mlp(void* handle)
     return EXL2_OK;
 }
 
-// q_mlp_forward_ (ext_qmlp.cpp:87-118 -> q_mlp.cu:153-236): x (+)= act(n Wg) * (n Wu) Wd, n = rmsnorm(x); in place on x
-int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream)
+// gate | up from `ns` (in_mode A_RMSNORM: the pre-norm rides in the staging of the rows; A_PLAIN: ns is already normed), act * up in the
+// staging of down, down into down_dst
+static int q_mlp_projections(QMLP* m, const f16* ns, int in_mode, f16* down_dst, int down_mode, int rows, void* stream)
 {
-    EXL2_REQUIRE(handle && x, "q_mlp_forward_: null argument");
-    QMLP* m = (QMLP*)handle;
-    if (rows <= 0) return EXL2_OK;
-    EXL2_REQUIRE(rows <= m->max_rows, "q_mlp_forward_: %d rows exceed max_rows %d", rows, m->max_rows);
-    EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
-                 "q_mlp_forward_: handle was made without scratch (tensor-parallel load)");
-    const int hidden = m->up->height;
     const bool gptq = m->up->is_gptq;
     const bool skinny = rows <= MAX_GEMV_ROWS;
-    f16* down_dst = m->post_layernorm ? m->temp_state : (f16*)x;
-    const int down_mode = (m->post_layernorm || !m->has_residual) ? C_STORE : C_ACCUM;
     GemvJob jobs[2];
-
-    const f16* ns = (const f16*)x;
-    const int in_mode = m->layernorm ? A_RMSNORM : A_PLAIN;     // norm in the staging of the rows (decode prologue / prefill pre-pass)
     int n = 0;
     if (m->gate) { fill_job(jobs[n], m->gate, ns, m->temp_a, in_mode, C_STORE); n++; fill_job(jobs[n], m->up, ns, m->temp_b, in_mode, C_STORE); n++; }
     else         { fill_job(jobs[n], m->up, ns, m->temp_a, in_mode, C_STORE); n++; }
-    for (int i = 0; i < n; i++) { jobs[i].norm_w = m->layernorm; jobs[i].norm_eps = m->norm_epsilon; }
+    if (in_mode == A_RMSNORM) for (int i = 0; i < n; i++) { jobs[i].norm_w = m->layernorm; jobs[i].norm_eps = m->norm_epsilon; }
     if (n == 2) jobs[1].rows_as_prev = m->gu_same_perm ? 1 : 0;
     // decode-shaped calls: gate / up write their columns straight into down's packed (act-order) row order, so down
     // stages a contiguous row instead of gathering through q_perm (temp_a / temp_b have no other reader)
@@ -980,9 +1048,58 @@ int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream)
         if (scatter) d.m.perm = nullptr;
     }
     LAUNCH_JOBS(&d, 1, rows, m->down->is_gptq, stream, "q_mlp_forward_");
+    return EXL2_OK;
+}
+
+// q_mlp_forward_ (ext_qmlp.cpp:87-118 -> q_mlp.cu:153-236): x (+)= act(n Wg) * (n Wu) Wd, n = rmsnorm(x); in place on x
+int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream)
+{
+    EXL2_REQUIRE(handle && x, "q_mlp_forward_: null argument");
+    QMLP* m = (QMLP*)handle;
+    if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(rows <= m->max_rows, "q_mlp_forward_: %d rows exceed max_rows %d", rows, m->max_rows);
+    EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
+                 "q_mlp_forward_: handle was made without scratch (tensor-parallel load)");
+    const int hidden = m->up->height;
+    if (m->residual_fp32)
+    {
+        // x is fp32 (q_mlp.cu:183, :230): pre-norm fp32 -> fp16 temp_state in a launch of its own, the projections from it, down stored
+        // back into it, the post norm added into x in fp32
+        EXL2_REQUIRE(!chain_sync_active(), "q_mlp_forward_: an fp32 residual stream is not built for the overlapped chain");
+        int rc = exl2_rms_norm(x, m->layernorm, m->temp_state, m->norm_epsilon, rows, hidden, 0, 1, 0, stream);
+        if (rc) return rc;
+        rc = q_mlp_projections(m, m->temp_state, A_PLAIN, m->temp_state, C_STORE, rows, stream);
+        if (rc) return rc;
+        return exl2_rms_norm(m->temp_state, m->post_layernorm, x, m->norm_epsilon, rows, hidden, 1, 0, 1, stream);
+    }
+    f16* down_dst = m->post_layernorm ? m->temp_state : (f16*)x;
+    const int down_mode = (m->post_layernorm || !m->has_residual) ? C_STORE : C_ACCUM;
+    // norm in the staging of the rows (decode prologue / prefill pre-pass)
+    const int rc = q_mlp_projections(m, (const f16*)x, m->layernorm ? A_RMSNORM : A_PLAIN, down_dst, down_mode, rows, stream);
+    if (rc) return rc;
     if (m->post_layernorm)
         return exl2_rms_norm(m->temp_state, m->post_layernorm, x, m->norm_epsilon, rows, hidden, 1, 0, 0, stream);
     return EXL2_OK;
+}
+
+// The MLP for a caller that owns the norms (include/exl2_hip.h): xn is the normed fp16 input (it may be temp_state itself), down's
+// output stays in temp_state.
+int exl2_q_mlp_forward_normed(void* handle, const void* xn, int rows, void* stream)
+{
+    EXL2_REQUIRE(handle && xn, "q_mlp_forward_normed: null argument");
+    QMLP* m = (QMLP*)handle;
+    if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(rows <= m->max_rows, "q_mlp_forward_normed: %d rows exceed max_rows %d", rows, m->max_rows);
+    EXL2_REQUIRE(m->post_layernorm && m->temp_state && m->temp_a && (!m->gate || m->temp_b),
+                 "q_mlp_forward_normed: the handle needs a post norm and its scratch");
+    EXL2_REQUIRE(!chain_sync_active(), "q_mlp_forward_normed: not built for the overlapped chain");
+    return q_mlp_projections(m, (const f16*)xn, A_PLAIN, m->temp_state, C_STORE, rows, stream);
+}
+
+int exl2_q_mlp_residual_fp32(void* handle)
+{
+    EXL2_REQUIRE(handle, "q_mlp_residual_fp32: null argument");
+    return ((QMLP*)handle)->residual_fp32 ? 1 : 0;
 }
 
 // x = act(x) in place, fp16 [rows, width] (the gateless MLP with adapters: fp_act_kernel of q_mlp.cu:212-213; without adapters the
@@ -1003,6 +1120,7 @@ int exl2_q_mlp_set_loras(void* handle, int n_loras, const uint64_t* ids, const v
 {
     EXL2_REQUIRE(handle && n_loras >= 0 && (n_loras == 0 || (ids && a && b && ranks)), "q_mlp_set_loras: null argument");
     QMLP* m = (QMLP*)handle;
+    EXL2_REQUIRE(!m->residual_fp32, "q_mlp_set_loras: adapters are not built for an fp32 residual stream");
     EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
                  "q_mlp_set_loras: handle was made without scratch (tensor-parallel load)");
     const int n_gu = m->gate ? 2 : 1;
@@ -1046,6 +1164,7 @@ int exl2_q_mlp_forward_loras(void* handle, void* x, int rows, int n_loras, const
     EXL2_REQUIRE(!chain_sync_active(), "q_mlp_forward_: adapters are not built for the overlapped chain");
     QMLP* m = (QMLP*)handle;
     if (rows <= 0) return EXL2_OK;
+    EXL2_REQUIRE(!m->residual_fp32, "q_mlp_forward_: adapters are not built for an fp32 residual stream");
     EXL2_REQUIRE(rows <= m->max_rows, "q_mlp_forward_: %d rows exceed max_rows %d", rows, m->max_rows);
     EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
                  "q_mlp_forward_: handle was made without scratch (tensor-parallel load)");

@@ -37,6 +37,7 @@ class ExtC:
     def __init__(self, lib: _lib.Lib | None = None, allow_cpu: bool = False):
         self._lib = lib
         self.allow_cpu = allow_cpu
+        self._fp32_modules = set()          # q_attn / q_mlp handles made with residual_fp32: their forwards take x as fp32
 
     @property
     def lib(self) -> _lib.Lib:
@@ -664,16 +665,22 @@ class ExtC:
             int(max_rows), int(hidden_size), int(num_heads), int(num_kv_heads), int(head_dim), int(max_seq_len),
             int(has_residual), int(rope_style), int(sincos_size), self._ptr(q_norm), self._ptr(k_norm),
             self._ptr(post_layernorm), self._ptr(post_layernorm_bias), int(residual_fp32), int(use_graphs)))
+        if residual_fp32: self._fp32_modules.add(int(h.value))
         return int(h.value)
 
     def free_q_attn(self, handle: int) -> None:
+        self._fp32_modules.discard(handle)
         self.lib.check(self.lib.exl2_free_q_attn(handle))
+
+    def _x_dtype(self, handle):
+        """The residual stream's dtype for a module handle: the forwards reject an x that does not match it (ext_qattn.cpp:133-134)."""
+        return torch.float32 if handle in self._fp32_modules else torch.float16
 
     def q_attn_forward_1(self, q_attn, x, batch_size, q_len, past_len, past_lens, q_temp, k_temp, v_temp, sin, cos,
                          loras=None, loras_temp=None, apply_rope: bool = True) -> None:
         """loras: the ids of the adapters to apply (q_attn_set_loras), any iterable of ints; loras_temp is accepted and unused (the
         handle keeps its own scratch)."""
-        args = (q_attn, self._ptr(x, torch.float16, "x"), int(batch_size), int(q_len), int(past_len),
+        args = (q_attn, self._ptr(x, self._x_dtype(q_attn), "x"), int(batch_size), int(q_len), int(past_len),
                 self._ptr(past_lens, torch.int32, "past_lens"), self._ptr(q_temp, torch.float16, "q_temp"),
                 self._ptr(k_temp, torch.float16, "k_temp"), self._ptr(v_temp, torch.float16, "v_temp"),
                 self._ptr(sin), self._ptr(cos), int(apply_rope))
@@ -686,13 +693,27 @@ class ExtC:
     def q_attn_forward_2(self, q_attn, x, attn_output, batch_size, q_len, loras=None, loras_temp=None) -> None:
         if loras:
             n, ids = self._lora_ids(loras)
-            self.lib.check(self.lib.exl2_q_attn_forward_2_loras(q_attn, self._ptr(x, torch.float16, "x"),
+            self.lib.check(self.lib.exl2_q_attn_forward_2_loras(q_attn, self._ptr(x, self._x_dtype(q_attn), "x"),
                                                                 self._ptr(attn_output, torch.float16, "attn_output"),
                                                                 int(batch_size), int(q_len), n, ids, self._stream(x)))
             return
-        self.lib.check(self.lib.exl2_q_attn_forward_2(q_attn, self._ptr(x, torch.float16, "x"),
+        self.lib.check(self.lib.exl2_q_attn_forward_2(q_attn, self._ptr(x, self._x_dtype(q_attn), "x"),
                                                       self._ptr(attn_output, torch.float16, "attn_output"),
                                                       int(batch_size), int(q_len), self._stream(x)))
+
+    def q_attn_forward_1_normed(self, q_attn, xn, batch_size, q_len, past_len, past_lens, q_temp, k_temp, v_temp, sin, cos,
+                                apply_rope: bool = True) -> None:
+        """q_attn_forward_1 for a caller that owns the norms: xn is the already-normed fp16 input, no pre-norm is launched."""
+        self.lib.check(self.lib.exl2_q_attn_forward_1_normed(
+            q_attn, self._ptr(xn, torch.float16, "xn"), int(batch_size), int(q_len), int(past_len),
+            self._ptr(past_lens, torch.int32, "past_lens"), self._ptr(q_temp, torch.float16, "q_temp"),
+            self._ptr(k_temp, torch.float16, "k_temp"), self._ptr(v_temp, torch.float16, "v_temp"),
+            self._ptr(sin), self._ptr(cos), int(apply_rope), self._stream(xn)))
+
+    def q_attn_forward_2_normed(self, q_attn, attn_output, batch_size, q_len) -> None:
+        """o_proj of a post-norm handle into the handle's temp_state; the post norm is the caller's (norm_bridge)."""
+        self.lib.check(self.lib.exl2_q_attn_forward_2_normed(q_attn, self._ptr(attn_output, torch.float16, "attn_output"),
+                                                             int(batch_size), int(q_len), self._stream(attn_output)))
 
     def make_q_mlp(self, layernorm, layernorm_bias, layernorm_is_rms, norm_epsilon, q_gate, q_up, q_down, temp_state,
                    temp_a, temp_b, temp_dq, max_rows, act_gelu, has_residual, post_layernorm, post_layernorm_bias,
@@ -703,20 +724,29 @@ class ExtC:
             q_gate or None, q_up, q_down, self._ptr(temp_state), self._ptr(temp_a), self._ptr(temp_b),
             self._ptr(temp_dq), int(max_rows), int(act_gelu), int(has_residual), self._ptr(post_layernorm),
             self._ptr(post_layernorm_bias), int(residual_fp32), int(use_graphs)))
+        if residual_fp32: self._fp32_modules.add(int(h.value))
         return int(h.value)
 
     def free_q_mlp(self, handle: int) -> None:
+        self._fp32_modules.discard(handle)
         self.lib.check(self.lib.exl2_free_q_mlp(handle))
 
     def q_mlp_forward_(self, q_mlp, x, loras=None, loras_temp=None) -> None:
         hidden = x.shape[-1]
         if loras:
             n, ids = self._lora_ids(loras)
-            self.lib.check(self.lib.exl2_q_mlp_forward_loras(q_mlp, self._ptr(x, torch.float16, "x"), x.numel() // hidden, n, ids,
+            self.lib.check(self.lib.exl2_q_mlp_forward_loras(q_mlp, self._ptr(x, self._x_dtype(q_mlp), "x"), x.numel() // hidden, n, ids,
                                                              self._stream(x)))
             return
-        self.lib.check(self.lib.exl2_q_mlp_forward(q_mlp, self._ptr(x, torch.float16, "x"), x.numel() // hidden,
+        self.lib.check(self.lib.exl2_q_mlp_forward(q_mlp, self._ptr(x, self._x_dtype(q_mlp), "x"), x.numel() // hidden,
                                                    self._stream(x)))
+
+    def q_mlp_forward_normed(self, q_mlp, xn) -> None:
+        """The MLP of a post-norm handle for a caller that owns the norms: xn fp16, already normed (it may be the handle's temp_state);
+        down_proj's output is left in temp_state."""
+        hidden = xn.shape[-1]
+        self.lib.check(self.lib.exl2_q_mlp_forward_normed(q_mlp, self._ptr(xn, torch.float16, "xn"), xn.numel() // hidden,
+                                                          self._stream(xn)))
 
     # ---- LoRA adapters (ext_qattn.cpp:193-254, ext_qmlp.cpp:120-169; csrc/lora.hip) ------------------------------------------
 
@@ -962,6 +992,39 @@ class ExtC:
                                                 self._ptr(dst, torch.float16, "dst"), src.numel(), self._stream(src)))
 
     # ---- decode-loop utilities + graphs (ours; no reference counterpart at the ext_c level) ----------------------------
+
+    def embed_rows_f32(self, table, ids, out, scale: float = 1.0) -> None:
+        """out fp32 [rows, hidden] = float(table[ids]) * scale (embedding.py:184-187); scale is rounded to fp32, one multiply."""
+        self.lib.check(self.lib.exl2_embed_rows_f32(self._ptr(table, torch.float16, "table"), self._ptr(ids, torch.int32, "ids"),
+                                                    self._ptr(out, torch.float32, "out"), ids.numel(), table.shape[-1],
+                                                    table.shape[0], float(scale), self._stream(out)))
+
+    def norm_bridge(self, t, x, w_post, w_next, n, epsilon: float) -> bool:
+        """x fp32 += rmsnorm(t fp16) * w_post; then, with w_next, n fp16 = rmsnorm(x) * w_next -- one launch (n may be t).  False =
+        not covered (hidden > 8192): nothing was launched, run the two rms_norm launches."""
+        dim = x.shape[-1]
+        if t.shape != x.shape or w_post.shape[0] != dim: raise RuntimeError("norm_bridge: incompatible shapes")
+        if not _is_none(w_next) and (_is_none(n) or n.shape != x.shape or w_next.shape[0] != dim):
+            raise RuntimeError("norm_bridge: incompatible shapes")
+        rc = self.lib.check(self.lib.exl2_norm_bridge(
+            self._ptr(t, torch.float16, "t"), self._ptr(x, torch.float32, "x"), self._ptr(w_post, torch.float16, "w_post"),
+            self._ptr(w_next, torch.float16, "w_next"), None if _is_none(w_next) else self._ptr(n, torch.float16, "n"),
+            float(epsilon), x.numel() // dim, dim, self._stream(x)))
+        return rc == 0
+
+    def rms_norm_add(self, t, w, x, epsilon: float) -> None:
+        """x += rmsnorm(t) * w: the post norm of a post-norm block (q_attn.cu:337-339), t fp16, x fp16 or fp32."""
+        dim = x.shape[-1]
+        if t.shape != x.shape or w.shape[0] != dim: raise RuntimeError("rms_norm_add: incompatible shapes")
+        self.lib.check(self.lib.exl2_rms_norm(self._ptr(t, torch.float16, "t"), self._ptr(w, torch.float16, "w"), self._ptr(x, None, "x"),
+                                              float(epsilon), x.numel() // dim, dim, 1, 0, int(x.dtype == torch.float32), self._stream(x)))
+
+    def softcap_(self, x, scale: float) -> None:
+        """ext_element.cpp:28-50: x = scale * tanh(x / scale) in place, x float or half."""
+        if x.dtype == torch.float32: is32 = 1
+        elif x.dtype == torch.float16: is32 = 0
+        else: raise RuntimeError("softcap_ wrong dtype")
+        self.lib.check(self.lib.exl2_softcap(self._ptr(x, None, "x"), x.numel(), float(scale), is32, self._stream(x)))
 
     def embed_rows(self, table, ids, out) -> None:
         self.lib.check(self.lib.exl2_embed_rows(self._ptr(table, torch.float16, "table"),

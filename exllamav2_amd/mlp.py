@@ -20,11 +20,16 @@ class ExLlamaV2MLP:
         cfg, m = self.model.config, self.model
         for lin in (self.gate_proj, self.up_proj, self.down_proj):
             lin.load(ck[lin.key])
-        self.post_attention_layernorm = ck[self.key + ".post_attention_layernorm"]
+        post = getattr(cfg, "post_norms", False)
+        # with post norms the MLP's pre-norm is `.pre_feedforward_layernorm` and `.post_feedforward_layernorm` follows down_proj
+        # (architecture.py:566-569); `.post_attention_layernorm` then belongs to the attention module
+        self.post_attention_layernorm = m.norm_weight(ck[self.key + (".pre_feedforward_layernorm" if post else ".post_attention_layernorm")])
+        self.post_layernorm = m.norm_weight(ck[self.key + ".post_feedforward_layernorm"]) if post else None
         self.q_handle = self.ext.make_q_mlp(                                     # mlp.py:204-223
             self.post_attention_layernorm, none_tensor, True, cfg.norm_eps,
             self.gate_proj.q_handle, self.up_proj.q_handle, self.down_proj.q_handle,
-            m.temp_state, m.temp_a, m.temp_b, none_tensor, m.max_rows, False, True, none_tensor, none_tensor, False, False)
+            m.temp_state, m.temp_a, m.temp_b, none_tensor, m.max_rows, getattr(cfg, "mlp_act_func", "silu") == "gelu", True,
+            none_tensor if self.post_layernorm is None else self.post_layernorm, none_tensor, bool(getattr(cfg, "residual_fp32", False)), False)
         return self
 
     def unload(self):
@@ -43,3 +48,8 @@ class ExLlamaV2MLP:
         row pre-pass + dequantize-into-MFMA GEMMs, csrc/modules.hip:exl2_q_mlp_forward).  loras: the ExLlamaV2Lora adapters to apply."""
         self.ext.q_mlp_forward_(self.q_handle, hidden_states, loras=[id(l) for l in loras] if loras else None)
         return hidden_states
+
+    def forward_normed(self, xn: torch.Tensor):
+        """The MLP for a caller that owns the norms (a post-norm block): xn fp16 [rows, hidden], already normed; down_proj's output is
+        left in the model's temp_state, the post norm is the caller's (ext.norm_bridge)."""
+        self.ext.q_mlp_forward_normed(self.q_handle, xn)

@@ -18,9 +18,10 @@ from .moe_mlp import ExLlamaV2MoEMLP
 from .rmsnorm import ExLlamaV2RMSNorm
 
 
-def rope_tables(cfg: ExLlamaV2Config, device):
-    """device.py:118-169: fp16 sin/cos [max_seq_len, head_dim]."""
-    inv_freq = 1.0 / (cfg.rotary_embedding_base ** (torch.arange(0, cfg.head_dim, 2, device=device).float() / cfg.head_dim))
+def rope_tables(cfg: ExLlamaV2Config, device, base: float | None = None):
+    """device.py:118-169: fp16 sin/cos [max_seq_len, head_dim]; `base`: another rope base than the config's (rotary_embedding_base_alt)."""
+    base = cfg.rotary_embedding_base if base is None else base
+    inv_freq = 1.0 / (base ** (torch.arange(0, cfg.head_dim, 2, device=device).float() / cfg.head_dim))
     t = torch.arange(cfg.max_seq_len, device=device, dtype=torch.float32)
     freqs = torch.einsum("i,j->ij", t, inv_freq)
     emb = torch.cat((freqs, freqs), dim=-1) if cfg.rope_style == 2 else torch.repeat_interleave(freqs, 2, dim=-1)
@@ -51,6 +52,8 @@ class ExLlamaV2:
         self.attn_counters = torch.zeros((16384,), dtype=torch.int32, device=dev)     # split hand-off tickets (attn.hip)
         self._dq = None                                   # reconstruct target of ExLlamaV2Linear.forward(force_recons=True)
         self.sin, self.cos = rope_tables(cfg, dev)
+        # windowed layers of a model whose local attention has its own rope base (Gemma-3) rotate with a second table
+        self.sin_alt, self.cos_alt = rope_tables(cfg, dev, cfg.rotary_embedding_base_alt) if cfg.rotary_embedding_base_alt else (None, None)
         self.modules = []
         self.layers = []
         self.embed_tokens = None
@@ -63,6 +66,19 @@ class ExLlamaV2:
         if self._dq is None or self._dq.numel() < k * n:
             self._dq = torch.empty((k * n,), dtype=torch.float16, device=device)
         return self._dq[:k * n].view(k, n)
+
+    def norm_weight(self, w: torch.Tensor) -> torch.Tensor:
+        """an RMSNorm weight as the kernels take it: the architecture's constant bias added in fp16 (rmsnorm.py:57-59)"""
+        b = float(getattr(self.config, "norm_constant_bias", 0.0) or 0.0)
+        return (w + b).to(torch.float16).contiguous() if b else w
+
+    def check_cache(self, cache) -> None:
+        """a clear error for a cache this model's attention cannot use (the attention modules raise the same at their first call)"""
+        if getattr(cache, "wbits", 0) and any(a.attend_extras(cache) is not None or getattr(a, "sin", self.sin) is not self.sin for a, _ in self.layers):
+            raise RuntimeError("a quantized cache together with a sliding window or a score cap is not built: the kernels that attend "
+                               "from the codes carry neither (use the FP16 cache)")
+        if getattr(cache, "wbits", 0) and self.config.softmax_scale() != self.config.head_dim ** -0.5:
+            raise RuntimeError("a quantized cache together with query_pre_attn_scalar is not built (use the FP16 cache)")
 
     def load(self, ck: dict, layers=None):
         """model.py:266-351: build the module handles from a checkpoint dict.  `layers` = the global layer indices this
@@ -83,7 +99,7 @@ class ExLlamaV2:
         vpad = (cfg.vocab_size + 31) // 32 * 32
         self.vocab_padded = vpad
         if "lm_head" in ck:
-            self.norm = ExLlamaV2RMSNorm(self.ext, "model.norm", ck["model.norm"], cfg.norm_eps)
+            self.norm = ExLlamaV2RMSNorm(self.ext, "model.norm", self.norm_weight(ck["model.norm"]), cfg.norm_eps)
             self.lm_head = ExLlamaV2Linear(self.ext, "lm_head", cfg.hidden_size, vpad, self).load(ck["lm_head"])
         if not self.loaded:
             ExLlamaV2._live_on_device[str(self.device)] = ExLlamaV2._live_on_device.get(str(self.device), 0) + 1
@@ -144,6 +160,8 @@ class ExLlamaV2:
         cfg = self.config
         b, q_len = input_ids.shape
         assert b * q_len <= self.max_rows, "chunk larger than the scratch arena"
+        if cfg.residual_fp32:
+            return self._forward_chunk_fp32(input_ids, cache, past_len, cache_seqlens, block_table, last_id_only, preprocess_only, loras)
         x = self.embed_tokens[input_ids.to(self.device).reshape(-1)].view(b, q_len, cfg.hidden_size).contiguous()
         for attn, mlp in self.layers:
             if loras:
@@ -158,6 +176,35 @@ class ExLlamaV2:
             x = x[:, -1:, :].contiguous()
         x = self.norm.forward(x)
         logits = self.lm_head.forward(x)
+        return logits[..., :cfg.vocab_size]
+
+    def embed_scale(self) -> float:
+        cfg = self.config
+        return float(cfg.hidden_size) ** 0.5 if cfg.normalize_embeddings else 1.0
+
+    def _forward_chunk_fp32(self, input_ids, cache, past_len, cache_seqlens, block_table, last_id_only, preprocess_only, loras):
+        """forward_chunk of a model with an fp32 residual stream (Gemma-2 / Gemma-3): fp32 x from the scaled embedding
+        (embedding.py:184-187), every module through its handle (pre-norm fp32 -> fp16, post norm added in fp32), the final norm
+        fp32 -> fp16, the head, the cap on the fp16 logits (model.py:1043-1044)."""
+        cfg, ext = self.config, self.ext
+        if loras:
+            raise RuntimeError("LoRA adapters are not built for a model with an fp32 residual stream")
+        b, q_len = input_ids.shape
+        ids = input_ids.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+        x = torch.empty((b, q_len, cfg.hidden_size), dtype=torch.float32, device=self.device)
+        ext.embed_rows_f32(self.embed_tokens, ids, x.view(b * q_len, cfg.hidden_size), self.embed_scale())
+        for attn, mlp in self.layers:
+            attn.forward(x, cache, past_len, cache_seqlens, block_table)
+            mlp.forward(x)
+        if preprocess_only:
+            return None
+        if last_id_only:
+            x = x[:, -1:, :].contiguous()
+        xn = torch.empty(x.shape, dtype=torch.float16, device=self.device)
+        ext.rms_norm(x.view(-1, cfg.hidden_size), self.norm.weight, xn.view(-1, cfg.hidden_size), cfg.norm_eps)
+        logits = self.lm_head.forward(xn)
+        if cfg.final_logit_softcapping:
+            ext.softcap_(logits, cfg.final_logit_softcapping)
         return logits[..., :cfg.vocab_size]
 
     def forward(self, input_ids: torch.Tensor, cache, last_id_only: bool = True, preprocess_only: bool = False,
@@ -237,8 +284,15 @@ class GreedyGraphDecoder:
         self.cache_seqlens = torch.zeros((batch_size,), dtype=torch.int32, device=dev)
         self.ids = torch.zeros((batch_size,), dtype=torch.int32, device=dev)
         self.history = torch.zeros((batch_size, cache.max_seq_len + 2), dtype=torch.int32, device=dev)
-        self.x = torch.zeros((batch_size, 1, cfg.hidden_size), dtype=torch.float16, device=dev)
-        self.xn = torch.zeros_like(self.x)
+        self.fp32 = bool(cfg.residual_fp32)
+        if self.fp32 and self.loras:
+            raise RuntimeError("LoRA adapters are not built for a model with an fp32 residual stream")
+        model.check_cache(cache)
+        self.x = torch.zeros((batch_size, 1, cfg.hidden_size), dtype=torch.float32 if self.fp32 else torch.float16, device=dev)
+        self.xn = torch.zeros((batch_size, 1, cfg.hidden_size), dtype=torch.float16, device=dev)
+        # fp32 residual stream: one launch for the two norms at every module boundary (ext.norm_bridge); EXL2_NORM_BRIDGE=0: the
+        # handles' own two launches (the A/B of tools/gemma_decode_bench.py, and the tests)
+        self.norm_bridge = self.fp32 and os.environ.get("EXL2_NORM_BRIDGE", "1") != "0"
         self.logits = torch.zeros((batch_size, model.vocab_padded), dtype=torch.float16, device=dev)
         self.graph = None
         # capture is not permitted on the legacy default stream: the decoder owns a stream (device.py:67-72 does too)
@@ -246,7 +300,7 @@ class GreedyGraphDecoder:
         self.chain = None
         self.pos = 0                  # host mirror of cache_seqlens (all rows advance together): bounds are checked here,
         self.limit = min(cache.max_seq_len, cfg.max_seq_len)      # the kernels index pages / sin-cos rows unchecked
-        if os.environ.get("EXL2_CHAIN", "1") != "0" and not self.loras:
+        if os.environ.get("EXL2_CHAIN", "1") != "0" and not self.loras and not self.fp32:
             self._setup_chain()
         if os.environ.get("EXL2_CHAIN_OVERLAP", "0") != "0" and (self.chain is None or "flags" not in self.chain):
             raise RuntimeError("EXL2_CHAIN_OVERLAP=1 asked for the experimental overlapped chain, but this model / cache / batch is "
@@ -258,6 +312,10 @@ class GreedyGraphDecoder:
         quantizer-written checkpoint), an FP16 or Q4 / Q6 / Q8 paged-view cache, a head on this device, <= 16 rows."""
         m, ext, cfg = self.model, self.model.ext, self.model.config
         if self.b > 16 or m.lm_head is None or m.embed_tokens is None:
+            return
+        # (the chained attention launch carries no window, score cap, softmax scale or second rotary table)
+        if cfg.softmax_scale() != cfg.head_dim ** -0.5 or cfg.final_logit_softcapping or any(
+                attn.attend_extras(self.cache) is not None or getattr(attn, "sin", m.sin) is not m.sin for attn, _ in m.layers):
             return
         if getattr(self.cache, "wbits", 0) and not all(attn.q4_chain_capable(self.cache) for attn, _ in m.layers):
             return
@@ -492,6 +550,8 @@ class GreedyGraphDecoder:
                                        "); unset EXL2_CHAIN_OVERLAP") from e
                 self.chain = None               # a shape outside the chained kernels: the module-by-module route below
         m, ext, cfg = self.model, self.model.ext, self.model.config
+        if self.fp32:
+            return self._launch_step_fp32()
         ext.embed_rows(m.embed_tokens, self.ids, self.x.view(self.b, cfg.hidden_size))
         for attn, mlp in m.layers:
             if self.loras:
@@ -503,6 +563,42 @@ class GreedyGraphDecoder:
         ext.rms_norm(self.x.view(self.b, -1), m.norm.weight, self.xn.view(self.b, -1), cfg.norm_eps)
         ext.gemm_half_q_half(self.xn.view(self.b, -1), m.lm_head.q_handle, self.logits)
         self._select_token()
+
+    def _launch_step_fp32(self):
+        """The step of a model with an fp32 residual stream (Gemma-2 / Gemma-3), module by module.  With the bridge the decoder owns the
+        norms: pre-norm of layer 0, then per layer the attention's `_normed` entries, a bridge (post-attention norm into x, pre-MLP
+        norm out), the MLP's `_normed` entry, a bridge (post-MLP norm into x, the next layer's pre-norm -- or the final norm -- out):
+        2 norm launches per layer instead of 4.  The normed rows and the projections' outputs share the model's temp_state."""
+        m, ext, cfg, b = self.model, self.model.ext, self.model.config, self.b
+        x2 = self.x.view(b, cfg.hidden_size)
+        ext.embed_rows_f32(m.embed_tokens, self.ids, x2, m.embed_scale())
+        ts = m.temp_state[:b]
+        bridged = self.norm_bridge
+        if bridged:
+            ext.rms_norm(x2, m.layers[0][0].pre_layernorm, ts, cfg.norm_eps)
+            for i, (attn, mlp) in enumerate(m.layers):
+                attn.forward_normed(ts, b, 1, self.cache, 0, self.cache_seqlens, self.block_table)
+                self._bridge(ts, x2, attn.post_layernorm, mlp.post_attention_layernorm, ts)
+                mlp.forward_normed(ts)
+                last = i + 1 == len(m.layers)
+                self._bridge(ts, x2, mlp.post_layernorm, m.norm.weight if last else m.layers[i + 1][0].pre_layernorm,
+                             self.xn.view(b, -1) if last else ts)
+        else:
+            for attn, mlp in m.layers:
+                attn.forward(self.x, self.cache, 0, self.cache_seqlens, self.block_table)
+                mlp.forward(self.x)
+            ext.rms_norm(x2, m.norm.weight, self.xn.view(b, -1), cfg.norm_eps)
+        ext.gemm_half_q_half(self.xn.view(b, -1), m.lm_head.q_handle, self.logits)
+        if cfg.final_logit_softcapping:
+            ext.softcap_(self.logits, cfg.final_logit_softcapping)
+        self._select_token()
+
+    def _bridge(self, t, x, w_post, w_next, n):
+        ext, eps = self.model.ext, self.model.config.norm_eps
+        if not ext.norm_bridge(t, x, w_post, w_next, n, eps):
+            # a hidden size the bridge does not cover: the two launches it stands for
+            ext.rms_norm_add(t, w_post, x, eps)
+            ext.rms_norm(x, w_next, n, eps)
 
     def _regroup(self, msg: str) -> bool:
         """a chained launch was declined ("<entry point>: shape not covered"): smaller row groups for launches of its K"""

@@ -223,17 +223,33 @@ def synth_checkpoint(cfg, device, recipe: str = "4.0bpw", seed: int = 0, act_ord
             ck[f"{p}.mlp.down_proj"] = make(inter, h, rec["down_proj"], device, gen, 0.5 / math.sqrt(inter), down_act_order and act_order)
         ck[f"{p}.input_layernorm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen)).half()
         ck[f"{p}.post_attention_layernorm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen)).half()
+        if getattr(cfg, "post_norms", False):
+            # Gemma-2 / Gemma-3 blocks: `.post_attention_layernorm` is the norm BEHIND o_proj, the MLP has its own pair (architecture.py:566-569).
+            # A generator of their own: the layer's other tensors are the same draws as without them
+            gen_p = gen_for(700000 + i)
+            ck[f"{p}.pre_feedforward_layernorm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen_p)).half()
+            ck[f"{p}.post_feedforward_layernorm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen_p)).half()
+        if getattr(cfg, "norm_constant_bias", 0.0):
+            # on disk such a weight lacks the constant the loader adds in fp16 (rmsnorm.py:57-59); w - 1 and (w - 1) + 1 are exact here
+            for nk in ("input_layernorm", "post_attention_layernorm", "pre_feedforward_layernorm", "post_feedforward_layernorm"):
+                if f"{p}.{nk}" in ck:
+                    ck[f"{p}.{nk}"] = ck[f"{p}.{nk}"] - cfg.norm_constant_bias
         if getattr(cfg, "use_qk_norm", False):
             # per-head q / k norm weights, every head its own row.  A generator of their own: the layer's other tensors are the
             # same draws with and without the norm
             gen_n = gen_for(500000 + i)
             ck[f"{p}.self_attn.q_norm"] = (1 + 0.1 * torch.randn(cfg.num_attention_heads, cfg.head_dim, device=device, generator=gen_n)).half()
             ck[f"{p}.self_attn.k_norm"] = (1 + 0.1 * torch.randn(cfg.num_key_value_heads, cfg.head_dim, device=device, generator=gen_n)).half()
+            if getattr(cfg, "norm_constant_bias", 0.0):                  # (headnorm.py:78-79: the loader adds it to these as well)
+                for nk in ("q_norm", "k_norm"):
+                    ck[f"{p}.self_attn.{nk}"] = ck[f"{p}.self_attn.{nk}"] - cfg.norm_constant_bias
     if with_embed:
         ck["model.embed_tokens"] = torch.randn(cfg.vocab_size, h, device=device, generator=gen_for(0)).half()
     if with_head:
         gen = gen_for(99991)
         ck["model.norm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen)).half()
+        if getattr(cfg, "norm_constant_bias", 0.0):
+            ck["model.norm"] = ck["model.norm"] - cfg.norm_constant_bias
         vpad = (cfg.vocab_size + 31) // 32 * 32                               # linear.py:82-88 pads out_features to x32
         ck["lm_head"] = make(h, vpad, rec["lm_head"], device, gen, s_attn, act_order)
         if structured_head:

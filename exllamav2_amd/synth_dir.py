@@ -39,6 +39,18 @@ def write_model_dir(path: str, cfg, ck: dict) -> str:
         # config.py:322-323: num_local_experts / num_experts_per_tok)
         config.update({"architectures": ["MixtralForCausalLM"], "model_type": "mixtral",
                        "num_local_experts": cfg.num_experts, "num_experts_per_tok": cfg.num_experts_per_token})
+    if getattr(cfg, "residual_fp32", False):
+        # Gemma-2 (architecture.py:554-576): fp32 residual stream, the four norms per layer, GELU, both soft caps.  The norm tensors
+        # of `ck` are already stored without the constant bias the reference's loader adds (synth.py; rmsnorm.py:57-59), and the
+        # quantized lm_head is found under its own key before the tied-embedding alternative (module.py:107-112)
+        if getattr(cfg, "use_qk_norm", False) or getattr(cfg, "sliding_window_pattern", 1) > 1:
+            raise NotImplementedError("write_model_dir: only the Gemma-2 form of an fp32-residual config is written")
+        config.update({"architectures": ["Gemma2ForCausalLM"], "model_type": "gemma2", "hidden_act": "gelu_pytorch_tanh",
+                       "hidden_activation": "gelu_pytorch_tanh", "head_dim": cfg.head_dim,
+                       "attn_logit_softcapping": cfg.attn_logit_softcapping or None,
+                       "final_logit_softcapping": cfg.final_logit_softcapping or None,
+                       "query_pre_attn_scalar": cfg.query_pre_attn_scalar or cfg.head_dim,
+                       "sliding_window": cfg.sliding_window})
     with open(os.path.join(path, "config.json"), "w") as f:
         json.dump(config, f)
     return path

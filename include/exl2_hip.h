@@ -315,6 +315,21 @@ int exl2_make_q_mlp(void** handle, const void* layernorm, const void* layernorm_
                     const void* post_layernorm, const void* post_layernorm_bias, int residual_fp32, int use_graphs);
 int exl2_free_q_mlp(void* handle);
 int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream);
+/* fp32 residual stream (Gemma-2 / Gemma-3: architecture.py:576, :601).  residual_fp32 = 1 is accepted for a handle with an RMS pre-norm
+   and a post norm (the reference's sanity check, architecture.py:955-957); never chain-capable.  The forwards above then take x as fp32
+   [rows, hidden] in the reference's order (q_attn.cu:268-279, :337-339, q_mlp.cu:183, :230): pre-norm fp32 -> fp16 temp_state in a launch
+   of its own, the projections from temp_state, o_proj / down_proj stored to temp_state, post norm added into x, fp16 in, fp32 out.
+   Adapters are refused on such a handle (the reference adds them into `(half*) hidden_state`, q_attn.cu:344).
+   The `_normed` entries are the same modules for a caller that owns the norms (any handle with a post norm): xn is the already-normed
+   fp16 input, no pre-norm is launched, and the output projection is LEFT in temp_state (the buffer given to make_q_*): the caller runs the
+   post norm, e.g. exl2_norm_bridge.  exl2_q_attn_residual_fp32 / exl2_q_mlp_residual_fp32: 1 for such a handle, else 0. */
+int exl2_q_attn_forward_1_normed(void* handle, const void* xn, int batch_size, int q_len, int past_len, const int* past_lens,
+                                 void* temp_q, void* temp_k, void* temp_v, const void* sin, const void* cos, int apply_rope,
+                                 void* stream);
+int exl2_q_attn_forward_2_normed(void* handle, const void* attn_output, int batch_size, int q_len, void* stream);
+int exl2_q_mlp_forward_normed(void* handle, const void* xn, int rows, void* stream);
+int exl2_q_attn_residual_fp32(void* handle);
+int exl2_q_mlp_residual_fp32(void* handle);
 
 /* ---- LoRA adapters (csrc/lora.hip; replaces apply_loras_cuda, cuda/lora.cu:5-34) ---------------------------------------------------
    out[rows, N] += sum over the listed adapters l of fp16(x[rows, K] A_l[K, r_l]) B_l[r_l, N]: fp32 accumulation on the matrix
@@ -462,6 +477,19 @@ int exl2_prefill_route_info(int* out4);
 /* ---- decode-loop utilities and graphs (replace cuda/graph.cu and the host-side embedding / argmax round trips) ------- */
 
 int exl2_embed_rows(const void* table, const int* ids, void* out, int rows, int hidden, int vocab, void* stream);
+/* out[r] fp32 = float(table[ids[r]]) * scale, one fp32 multiply (embedding.py:184-187: `.float()`, then `*= hidden_size ** 0.5` for
+   architectures that normalise their embeddings); ids are clamped to the table as exl2_embed_rows clamps them. */
+int exl2_embed_rows_f32(const void* table, const int* ids, void* out, int rows, int hidden, int vocab, float scale, void* stream);
+/* The two norms that meet at a module boundary of an fp32-residual model, in one launch (csrc/gemma_ops.hip): t fp16 [rows, dim] (what
+   o_proj / down_proj stored), x fp32 [rows, dim].  x += rmsnorm(t) * w_post, bit for bit exl2_rms_norm(t, w_post, x, eps, rows, dim,
+   1, 0, 1); then, unless w_next is null, n = fp16(rmsnorm(x) * w_next), the contract of exl2_rms_norm(x, w_next, n, eps, rows, dim, 0,
+   1, 0) up to the fp32 order of its sum of squares.  n may alias t.  Returns 0, or 1 = "not covered" when dim > 8192 (the row no longer
+   fits in a workgroup's registers): nothing was launched and the caller issues the two launches. */
+int exl2_norm_bridge(const void* t, void* x, const void* w_post, const void* w_next, void* n, float epsilon, int rows, int dim,
+                     void* stream);
+/* softcap_ (ext_element.cpp:28-50 -> softcap.cu:8-64): x = cap * tanhf(x / cap) in place over exactly numel elements, fp32 (is_fp32 = 1)
+   or fp16 through fp32 with round-to-nearest; any numel (the reference's fp16 launch mishandles an odd one). */
+int exl2_softcap(void* x, long long numel, float cap, int is_fp32, void* stream);
 /* greedy sampling on the device (test_inference.py:607 argmax; first maximum wins like torch.argmax).  history (nullable):
    token log [rows, hist_stride], written at hist_pos[row] + pos_inc; pos_inc != 0 also stores that sum back to hist_pos (the
    decode loop's position increment folded into this launch). */

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 
-def main(model_dir: str, out: str, steps: int = 4, flash: bool = False):
+def main(model_dir: str, out: str, steps: int = 4, flash: bool = False, prompt=(3, 17, 42, 7)):
     import exllamav2
     from exllamav2 import ExLlamaV2, ExLlamaV2Config, ExLlamaV2Cache
     from exllamav2.ext import ext_c
@@ -31,7 +31,7 @@ def main(model_dir: str, out: str, steps: int = 4, flash: bool = False):
     model = ExLlamaV2(config)
     model.load()
     cache = ExLlamaV2Cache(model, max_seq_len=256)
-    ids = torch.tensor([[3, 17, 42, 7]])
+    ids = torch.tensor([list(prompt)])
     # test_inference.py:604-609: logits = model.forward(ids[:, -1:], cache); sample = argmax; ids = cat
     logits = model.forward(ids, cache, last_id_only=False)
     all_logits = [logits.float().cpu().numpy()]
@@ -84,6 +84,9 @@ def main(model_dir: str, out: str, steps: int = 4, flash: bool = False):
             res[f"dyn_prompt_{i}"] = np.array(prompts[i])
         print("reference-on-dropin ok (dynamic generator, paged):", toks2)
     np.savez(out, **res)
+
+
+GEMMA_PROMPT = (3, 17, 42, 7, 100, 250, 9, 77, 31, 5, 64, 200)
 
 
 def main_tp(model_dir: str, out: str, steps: int = 4):
@@ -172,5 +175,9 @@ if __name__ == "__main__":
         main_split(sys.argv[1], sys.argv[2])
     elif len(sys.argv) > 3 and sys.argv[3] == "flash":
         main(sys.argv[1], sys.argv[2], flash=True)
+    elif len(sys.argv) > 3 and sys.argv[3] == "gemma":
+        # a synthetic Gemma-2 directory (exllamav2_amd/synth_dir.py): fp32 residual stream, post norms, soft caps; the flash_attn_func
+        # route, whose window_size = (W, W) / softcap the shim carries (attn.py:940-977), and a prompt longer than the window
+        main(sys.argv[1], sys.argv[2], flash=True, prompt=GEMMA_PROMPT)
     else:
         main(sys.argv[1], sys.argv[2])
