@@ -120,6 +120,14 @@ if _fast is not None:
         _fast.note_write(x)
         return _e.rms_norm_(x, w, epsilon)
 
+    def layer_norm(x, w, b, y, epsilon):
+        _fast.note_write(y)
+        return _e.layer_norm(x, w, b, y, epsilon)
+
+    def layer_norm_(x, w, b, epsilon):
+        _fast.note_write(x)
+        return _e.layer_norm_(x, w, b, epsilon)
+
     def head_norm(x, w, b, y, epsilon, rms):
         _fast.note_write(y)
         return _e.head_norm(x, w, b, y, epsilon, rms)
@@ -148,6 +156,8 @@ else:
     gemm_half_q_half = _e.gemm_half_q_half
     rms_norm = _e.rms_norm
     rms_norm_ = _e.rms_norm_
+    layer_norm = _e.layer_norm               # ext_norm.cpp -> layer_norm.cu (csrc/layer_norm.hip)
+    layer_norm_ = _e.layer_norm_
     head_norm = _e.head_norm
     head_norm_ = _e.head_norm_
     rope_ = _e.rope_
@@ -207,7 +217,7 @@ cache_rotate = _e.cache_rotate
 count_match = _e.count_match
 matrix_fp16_to_q4 = _e.matrix_fp16_to_q4
 matrix_q4_to_fp16 = _e.matrix_q4_to_fp16
-for _n in ("layer_norm", "layer_norm_", "gen_mrope_pos_ids", "gemm_half_half_half",
+for _n in ("gen_mrope_pos_ids", "gemm_half_half_half",
            "had_paley", "had_paley2", "pack_rows_4", "pack_columns", "quantize", "quantize_err", "quantize_range",
            "quantize_range_inplace", "sim_anneal", "logit_filter_exclusive",
            "dump_profile_results", "stloader_open_file", "stloader_close_file"):

@@ -99,6 +99,10 @@ PROTOTYPES = {
     "exl2_q_mlp_residual_fp32": (ci, [vp]),
     "exl2_norm_bridge": (ci, [vp, vp, vp, vp, vp, cf, ci, ci, vp]),
     "exl2_softcap": (ci, [vp, cll, cf, ci, vp]),
+    # LayerNorm models (csrc/layer_norm.hip)
+    "exl2_layer_norm": (ci, [vp, vp, vp, vp, cf, ci, ci, ci, vp]),
+    "exl2_parallel_bridge": (ci, [vp, vp, vp, vp, vp, vp, vp, cf, ci, ci, vp]),
+    "exl2_add_f16": (ci, [vp, vp, cll, vp]),
     "exl2_embed_rows_f32": (ci, [vp, vp, vp, ci, ci, ci, cf, vp]),
     # LoRA adapters (csrc/lora.hip)
     "exl2_q_attn_set_loras": (ci, [vp, ci, vp, vp, vp, vp]),

@@ -46,7 +46,12 @@ class ExLlamaV2Attention:
         cfg, m = self.model.config, self.model
         for lin in (self.q_proj, self.k_proj, self.v_proj, self.o_proj):
             lin.load(ck[lin.key])
-        self.pre_layernorm = m.norm_weight(ck[self.key + ".input_layernorm"])
+        # a parallel block (Cohere) owns the one norm of the layer: its attention handle has neither norm nor residual and overwrites
+        # the normed rows it is given (parallel_decoder.py:47-55)
+        parallel = bool(getattr(cfg, "parallel_decoder_blocks", False))
+        ln = getattr(cfg, "norm", "rmsnorm") == "layernorm"
+        self.pre_layernorm = None if parallel else m.norm_weight(ck[self.key + ".input_layernorm"])
+        self.pre_layernorm_bias = None if parallel else ck.get(self.key + ".input_layernorm.bias")
         post = getattr(cfg, "post_norms", False)
         self.post_layernorm = m.norm_weight(ck[self.key + ".post_attention_layernorm"]) if post else None
         # per-layer sliding window and rotary table (model.py:111-121): window_left keys to the left, 0 = all
@@ -60,10 +65,12 @@ class ExLlamaV2Attention:
         qn = none_tensor if self.q_norm is None else self.q_norm
         kn = none_tensor if self.k_norm is None else self.k_norm
         self.q_handle = self.ext.make_q_attn(                                   # attn.py:300-330
-            self.pre_layernorm, none_tensor, True, bool(getattr(cfg, "headnorm_rms", True)), cfg.norm_eps,
+            none_tensor if self.pre_layernorm is None else self.pre_layernorm,
+            none_tensor if self.pre_layernorm_bias is None else self.pre_layernorm_bias, not ln,
+            bool(getattr(cfg, "headnorm_rms", True)), cfg.norm_eps,
             self.q_proj.q_handle, self.k_proj.q_handle, self.v_proj.q_handle, self.o_proj.q_handle,
             m.temp_state, none_tensor, m.max_rows, cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads,
-            cfg.head_dim, cfg.max_seq_len, True, cfg.rope_style, cfg.head_dim, qn, kn,
+            cfg.head_dim, cfg.max_seq_len, not parallel, cfg.rope_style, cfg.head_dim, qn, kn,
             none_tensor if self.post_layernorm is None else self.post_layernorm,
             none_tensor, bool(getattr(cfg, "residual_fp32", False)), False)
         return self

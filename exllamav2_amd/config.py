@@ -38,6 +38,15 @@ class ExLlamaV2Config:
     sliding_window_pattern: int = 1         # > 1: every pattern-th layer is global (Gemma-3: 6)
     alternating_swa: bool = False           # windowed and global layers alternate (model.py:111-121)
     rotary_embedding_base_alt: float = 0.0  # rope base of the windowed layers when they have their own (Gemma-3: 10000)
+    # LayerNorm models (StarCoder2: architecture.py:656-676; Cohere: :704-721).  The defaults are every other family's.
+    norm: str = "rmsnorm"                   # "rmsnorm" | "layernorm" (mean removed, optional bias: layer_norm.cu)
+    norm_bias: bool = False                 # the LayerNorms carry a bias (StarCoder2)
+    parallel_decoder_blocks: bool = False   # one .input_layernorm feeds attention and MLP, x += attn; x += mlp (parallel_decoder.py)
+    mlp_gate: bool = True                   # False: ungated MLP, act(up) -> down (StarCoder2: c_fc / c_proj)
+    attention_bias_qkv: bool = False        # biased q / k / v projections
+    attention_bias_o: bool = False          # biased o_proj
+    mlp_bias: bool = False                  # biased MLP projections
+    logit_scale: float = 1.0                # folded into the head's scales at load (ext.py:336, :363)
 
     def __post_init__(self):
         if self.mlp_act_func not in ("silu", "gelu"):
@@ -50,6 +59,22 @@ class ExLlamaV2Config:
             raise ValueError("post_norms without residual_fp32 is not built in the native model")
         if self.residual_fp32 and self.num_experts:
             raise ValueError("a sparse-MoE MLP with an fp32 residual stream is not built")
+        if self.norm not in ("rmsnorm", "layernorm"):
+            raise ValueError(f"norm {self.norm!r}: 'rmsnorm' or 'layernorm'")
+        if self.norm == "layernorm" and (self.residual_fp32 or self.post_norms):
+            raise ValueError("residual_fp32 / post_norms together with LayerNorm are not built")
+        if self.norm == "layernorm" and self.num_experts:
+            raise ValueError("a sparse-MoE MLP with LayerNorm (DBRX) is not built")
+        if self.norm == "layernorm" and self.norm_constant_bias:
+            raise ValueError("norm_constant_bias belongs to RMSNorm architectures")
+        if self.norm != "layernorm" and (self.norm_bias or self.parallel_decoder_blocks):
+            raise ValueError("norm_bias / parallel_decoder_blocks are built for LayerNorm models only")
+        if self.num_experts and not self.mlp_gate:
+            raise ValueError("an ungated sparse-MoE MLP is not built")
+
+    @property
+    def layernorm(self) -> bool:
+        return self.norm == "layernorm"
 
     def layer_window(self, layer_idx: int) -> int:
         """Keys to the left a layer attends to, 0 = all (model.py:111-121): with alternating_swa, pattern > 1 windows the layers with
@@ -134,6 +159,52 @@ class ExLlamaV2Config:
                                                rotary_embedding_base=1e6, rotary_embedding_base_alt=10000.0, sliding_window=1024,
                                                sliding_window_pattern=6, use_qk_norm=True, attn_logit_softcapping=0.0,
                                                final_logit_softcapping=0.0, arch="gemma3") | kw))
+
+    # StarCoder2 and Cohere: the hyper-parameters below are written from memory of the published configs and could not be checked
+    # against them where this was written -- check them against the checkpoint's config.json before relying on them (nothing in the
+    # test-suite depends on them).
+    @staticmethod
+    def _starcoder2(**d):
+        """LayerNorm with bias, biased projections, ungated GELU MLP, NeoX rotary.  sliding_window is recorded as the checkpoints state
+        it; like the reference (model.py:111-121: no `swa` architecture flag for StarCoder2) no layer applies it."""
+        base = dict(vocab_size=49152, head_dim=128, max_seq_len=16384, norm_eps=1e-5, rotary_embedding_base=1e5, arch="starcoder2",
+                    norm="layernorm", norm_bias=True, mlp_gate=False, mlp_act_func="gelu", attention_bias_qkv=True,
+                    attention_bias_o=True, mlp_bias=True, sliding_window=4096)
+        base.update(d)
+        return ExLlamaV2Config(**base)
+
+    @staticmethod
+    def starcoder2_3b(**kw):
+        return ExLlamaV2Config._starcoder2(**(dict(hidden_size=3072, intermediate_size=12288, num_hidden_layers=30, num_attention_heads=24,
+                                                   num_key_value_heads=2) | kw))
+
+    @staticmethod
+    def starcoder2_7b(**kw):
+        return ExLlamaV2Config._starcoder2(**(dict(hidden_size=4608, intermediate_size=18432, num_hidden_layers=32, num_attention_heads=36,
+                                                   num_key_value_heads=4) | kw))
+
+    @staticmethod
+    def starcoder2_15b(**kw):
+        return ExLlamaV2Config._starcoder2(**(dict(hidden_size=6144, intermediate_size=24576, num_hidden_layers=40, num_attention_heads=48,
+                                                   num_key_value_heads=4) | kw))
+
+    @staticmethod
+    def _cohere(**d):
+        """bias-free LayerNorm, one norm per block feeding attention and MLP in parallel, GPT-J rotary, logit_scale"""
+        base = dict(vocab_size=256000, head_dim=128, max_seq_len=8192, norm_eps=1e-5, rotary_embedding_base=8e6, rope_style=1,
+                    arch="cohere", norm="layernorm", parallel_decoder_blocks=True, logit_scale=0.0625)
+        base.update(d)
+        return ExLlamaV2Config(**base)
+
+    @staticmethod
+    def command_r_35b(**kw):
+        return ExLlamaV2Config._cohere(**(dict(hidden_size=8192, intermediate_size=22528, num_hidden_layers=40, num_attention_heads=64,
+                                               num_key_value_heads=64) | kw))
+
+    @staticmethod
+    def aya_23_8b(**kw):
+        return ExLlamaV2Config._cohere(**(dict(hidden_size=4096, intermediate_size=14336, num_hidden_layers=32, num_attention_heads=32,
+                                               num_key_value_heads=8) | kw))
 
     @staticmethod
     def tiny_test(**kw):

@@ -32,6 +32,8 @@ int qgemv_launch(GemvJob* jobs, int n_jobs, int M, bool gptq, void* stream);
 extern "C" {
 int exl2_rms_norm(const void* x, const void* w, void* y, float epsilon, int rows, int dim,
                   int add_residual, int input_fp32, int output_fp32, void* stream);
+int exl2_layer_norm(const void* x, const void* w, const void* b, void* y, float epsilon, int rows, int dim, int add_residual,
+                    void* stream);
 int exl2_rope_qk(void* x_q, void* x_k, const void* sin, const void* cos, int batch_size,
                  int rows_per_batch_q, int rows_per_batch_k, int head_dim, int num_heads_q, int num_heads_k,
                  int past_len, const int* past_lens, int neox_style, int sincos_size, void* stream);
@@ -399,7 +401,7 @@ int exl2_make_q_moe_mlp(void** handle, const void* layernorm, const void* layern
 {
     (void)temp_gathered_state; (void)temp_dq; (void)layernorm_bias;
     EXL2_REQUIRE(handle && gate && w1 && w2 && w3, "make_q_moe_mlp: null argument");
-    EXL2_REQUIRE(layernorm && layernorm_is_rms, "make_q_moe_mlp: only RMSNorm pre-norm is built");
+    EXL2_REQUIRE(layernorm && layernorm_is_rms, "make_q_moe_mlp: only RMSNorm pre-norm is built (a LayerNorm MoE block is not)");
     EXL2_REQUIRE(num_experts == 4 || num_experts == 8 || num_experts == 16,
                  "make_q_moe_mlp: %d experts (the fused path covers 4, 8, 16 like q_mlp.cu:333)", num_experts);
     EXL2_REQUIRE(num_experts_per_token >= 1 && num_experts_per_token <= num_experts, "make_q_moe_mlp: bad experts per token");
@@ -686,7 +688,11 @@ int exl2_make_q_attn(void** handle, const void* layernorm, const void* layernorm
                      const void* post_layernorm_bias, int residual_fp32, int use_graphs)
 {
     EXL2_REQUIRE(handle && q_q_proj && q_k_proj && q_v_proj && q_o_proj, "make_q_attn: null projection handle");
-    EXL2_REQUIRE(!layernorm || layernorm_is_rms, "make_q_attn: only RMSNorm pre-norm is built (LayerNorm archs out of scope)");
+    // LayerNorm pre-norm (StarCoder2, Cohere: layernorm_is_rms == 0, optional bias): a launch of its own into temp_state
+    // (csrc/layer_norm.hip), the projections from there in their plain-input mode.  Not built next to it: a LayerNorm post norm, an fp32
+    // residual stream.
+    EXL2_REQUIRE(!layernorm || layernorm_is_rms || !post_layernorm, "make_q_attn: a post norm next to a LayerNorm pre-norm is not built");
+    EXL2_REQUIRE(!layernorm || layernorm_is_rms || !residual_fp32, "make_q_attn: an fp32 residual stream with LayerNorm is not built");
     // q / k head norm (Qwen3, Gemma3, OLMo2, Cohere: attn.py:196-198): weights [num_heads | num_kv_heads, head_dim], applied between
     // the projections and RoPE (q_attn.cu:285-289) by every forward_1 below
     EXL2_REQUIRE(!q_norm == !k_norm, "make_q_attn: q_norm and k_norm come together");
@@ -800,6 +806,13 @@ int exl2_q_attn_forward_1(void* handle, const void* x, int batch_size, int q_len
         if (rc) return rc;
         return q_attn_qkv_normed(a, a->temp_state, batch_size, q_len, past_len, past_lens, temp_q, temp_k, temp_v, sin, cos, apply_rope, stream);
     }
+    if (a->layernorm && !a->layernorm_is_rms)
+    {
+        // LayerNorm: one launch into temp_state; the projections read it as plain rows (the norm arms of the row staging are RMS arithmetic)
+        const int rc = exl2_layer_norm(x, a->layernorm, a->layernorm_bias, a->temp_state, a->norm_epsilon, rows, a->hidden_size, 0, stream);
+        if (rc) return rc;
+        return q_attn_qkv_normed(a, a->temp_state, batch_size, q_len, past_len, past_lens, temp_q, temp_k, temp_v, sin, cos, apply_rope, stream);
+    }
     const bool gptq = a->q_proj->is_gptq;
     EXL2_REQUIRE(a->k_proj->is_gptq == gptq && a->v_proj->is_gptq == gptq, "q_attn_forward_1: mixed EXL2/GPTQ projections");
     // RMSNorm rides in the staging of the rows for every row count: <= 16 rows in the decode kernel's prologue, above that in
@@ -889,6 +902,7 @@ int exl2_q_attn_set_loras(void* handle, int n_loras, const uint64_t* ids, const 
     QAttn* at = (QAttn*)handle;
     // (the reference adds adapter output into `(half*) hidden_state`, q_attn.cu:344: wrong for an fp32 x)
     EXL2_REQUIRE(!at->residual_fp32, "q_attn_set_loras: adapters are not built for an fp32 residual stream");
+    EXL2_REQUIRE(!at->layernorm || at->layernorm_is_rms, "q_attn_set_loras: adapters are not built for a LayerNorm pre-norm");
     EXL2_REQUIRE(at->temp_state || !at->layernorm, "q_attn_set_loras: handle was made without scratch (tensor-parallel load)");
     if (!at->lora_qkv)
     {
@@ -930,6 +944,7 @@ int exl2_q_attn_forward_1_loras(void* handle, const void* x, int batch_size, int
     const int rows = batch_size * q_len;
     if (rows <= 0) return EXL2_OK;
     EXL2_REQUIRE(!a->residual_fp32, "q_attn_forward_1: adapters are not built for an fp32 residual stream");
+    EXL2_REQUIRE(!a->layernorm || a->layernorm_is_rms, "q_attn_forward_1: adapters are not built for a LayerNorm pre-norm");
     EXL2_REQUIRE(a->temp_state || !a->layernorm, "q_attn_forward_1: handle was made without scratch (tensor-parallel load)");
     EXL2_REQUIRE(rows <= a->max_rows, "q_attn_forward_1: %d rows exceed max_rows %d", rows, a->max_rows);
     const bool gptq = a->q_proj->is_gptq;
@@ -985,7 +1000,9 @@ int exl2_make_q_mlp(void** handle, const void* layernorm, const void* layernorm_
                     const void* post_layernorm, const void* post_layernorm_bias, int residual_fp32, int use_graphs)
 {
     EXL2_REQUIRE(handle && q_up && q_down, "make_q_mlp: null projection handle");
-    EXL2_REQUIRE(!layernorm || layernorm_is_rms, "make_q_mlp: only RMSNorm pre-norm is built (LayerNorm archs out of scope)");
+    // LayerNorm pre-norm: as make_q_attn
+    EXL2_REQUIRE(!layernorm || layernorm_is_rms || !post_layernorm, "make_q_mlp: a post norm next to a LayerNorm pre-norm is not built");
+    EXL2_REQUIRE(!layernorm || layernorm_is_rms || !residual_fp32, "make_q_mlp: an fp32 residual stream with LayerNorm is not built");
     // fp32 residual stream: as make_q_attn (q_mlp.cu:183, :230)
     EXL2_REQUIRE(!residual_fp32 || (layernorm && layernorm_is_rms && post_layernorm),
                  "make_q_mlp: an fp32 residual stream needs an RMS pre-norm and a post norm");
@@ -1072,6 +1089,14 @@ int exl2_q_mlp_forward(void* handle, void* x, int rows, void* stream)
         if (rc) return rc;
         return exl2_rms_norm(m->temp_state, m->post_layernorm, x, m->norm_epsilon, rows, hidden, 1, 0, 1, stream);
     }
+    if (m->layernorm && !m->layernorm_is_rms)
+    {
+        // LayerNorm: one launch into temp_state, the projections from it as plain rows (no post norm next to it: make_q_mlp)
+        EXL2_REQUIRE(!chain_sync_active(), "q_mlp_forward_: a LayerNorm pre-norm is not built for the overlapped chain");
+        const int rc = exl2_layer_norm(x, m->layernorm, m->layernorm_bias, m->temp_state, m->norm_epsilon, rows, hidden, 0, stream);
+        if (rc) return rc;
+        return q_mlp_projections(m, m->temp_state, A_PLAIN, (f16*)x, m->has_residual ? C_ACCUM : C_STORE, rows, stream);
+    }
     f16* down_dst = m->post_layernorm ? m->temp_state : (f16*)x;
     const int down_mode = (m->post_layernorm || !m->has_residual) ? C_STORE : C_ACCUM;
     // norm in the staging of the rows (decode prologue / prefill pre-pass)
@@ -1121,6 +1146,7 @@ int exl2_q_mlp_set_loras(void* handle, int n_loras, const uint64_t* ids, const v
     EXL2_REQUIRE(handle && n_loras >= 0 && (n_loras == 0 || (ids && a && b && ranks)), "q_mlp_set_loras: null argument");
     QMLP* m = (QMLP*)handle;
     EXL2_REQUIRE(!m->residual_fp32, "q_mlp_set_loras: adapters are not built for an fp32 residual stream");
+    EXL2_REQUIRE(!m->layernorm || m->layernorm_is_rms, "q_mlp_set_loras: adapters are not built for a LayerNorm pre-norm");
     EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
                  "q_mlp_set_loras: handle was made without scratch (tensor-parallel load)");
     const int n_gu = m->gate ? 2 : 1;
@@ -1165,6 +1191,7 @@ int exl2_q_mlp_forward_loras(void* handle, void* x, int rows, int n_loras, const
     QMLP* m = (QMLP*)handle;
     if (rows <= 0) return EXL2_OK;
     EXL2_REQUIRE(!m->residual_fp32, "q_mlp_forward_: adapters are not built for an fp32 residual stream");
+    EXL2_REQUIRE(!m->layernorm || m->layernorm_is_rms, "q_mlp_forward_: adapters are not built for a LayerNorm pre-norm");
     EXL2_REQUIRE(rows <= m->max_rows, "q_mlp_forward_: %d rows exceed max_rows %d", rows, m->max_rows);
     EXL2_REQUIRE(m->temp_a && (!m->gate || m->temp_b) && (m->temp_state || !(m->layernorm || m->post_layernorm)),
                  "q_mlp_forward_: handle was made without scratch (tensor-parallel load)");

@@ -181,6 +181,53 @@ class ExtC:
         """ext_norm.cpp:58-85 (in place)."""
         self.rms_norm(x, w, x, epsilon)
 
+    def layer_norm(self, x, w, b, y, epsilon: float) -> None:
+        """ext_norm.cpp (layer_norm): y = layernorm(x) * w (+ b); x, y half [rows, dim]; `none_tensor` for b = no bias.  dim: a multiple
+        of 8 up to 16384 -- any other shape raises "shape not covered"."""
+        for t, n in ((x, "x"), (w, "w"), (y, "y")):
+            if t.dtype != torch.float16: raise RuntimeError(f"layer_norm: {n} must be half")
+        if x.shape[-1] != w.shape[0] or x.shape != y.shape: raise RuntimeError("layer_norm: x, w and y have incompatible shapes")
+        if not _is_none(b) and (b.dtype != torch.float16 or b.shape[0] != w.shape[0]):
+            raise RuntimeError("layer_norm: b must be half and shaped like w")
+        dim = x.shape[-1]
+        self.lib.check(self.lib.exl2_layer_norm(self._ptr(x, torch.float16, "x"), self._ptr(w, torch.float16, "w"),
+                                                self._ptr(b, torch.float16, "b"), self._ptr(y, torch.float16, "y"),
+                                                float(epsilon), x.numel() // dim, dim, 0, self._stream(x)))
+
+    def layer_norm_(self, x, w, b, epsilon: float) -> None:
+        """ext_norm.cpp (layer_norm_): in place."""
+        self.layer_norm(x, w, b, x, epsilon)
+
+    def layer_norm_add(self, t, w, b, y, epsilon: float) -> None:
+        """y += layernorm(t) * w (+ b): layer_norm_cuda's add_residual form (an fp16 add on the rounded value)."""
+        dim = t.shape[-1]
+        if t.shape != y.shape or w.shape[0] != dim: raise RuntimeError("layer_norm_add: incompatible shapes")
+        self.lib.check(self.lib.exl2_layer_norm(self._ptr(t, torch.float16, "t"), self._ptr(w, torch.float16, "w"),
+                                                self._ptr(b, torch.float16, "b"), self._ptr(y, torch.float16, "y"),
+                                                float(epsilon), t.numel() // dim, dim, 1, self._stream(t)))
+
+    def parallel_bridge(self, x, a, b, w, bias, n0, n1, epsilon: float) -> bool:
+        """x += a; x += b (fp16 adds in that order, parallel_decoder.py:141-142); then, with w, n0 (and n1) = layernorm(x) * w (+ bias),
+        bit for bit what layer_norm gives -- one launch.  a and b `none_tensor`: the norm only; w `none_tensor`: the adds only;
+        n1 `none_tensor`: one copy.  n0 may be a and n1 may be b.  False = shape not covered: nothing was launched, run add_f16_ twice
+        and layer_norm."""
+        dim = x.shape[-1]
+        if _is_none(a) != _is_none(b): raise RuntimeError("parallel_bridge: a and b come together")
+        for t in (a, b, n0, n1):
+            if not _is_none(t) and t.shape != x.shape: raise RuntimeError("parallel_bridge: incompatible shapes")
+        if not _is_none(w) and (w.shape[0] != dim or _is_none(n0) or (not _is_none(bias) and bias.shape[0] != dim)):
+            raise RuntimeError("parallel_bridge: incompatible shapes")
+        rc = self.lib.check(self.lib.exl2_parallel_bridge(
+            self._ptr(x, torch.float16, "x"), self._ptr(a, torch.float16, "a"), self._ptr(b, torch.float16, "b"),
+            self._ptr(w, torch.float16, "w"), self._ptr(bias, torch.float16, "bias"), self._ptr(n0, torch.float16, "n0"),
+            self._ptr(n1, torch.float16, "n1"), float(epsilon), x.numel() // dim, dim, self._stream(x)))
+        return rc == 0
+
+    def add_f16_(self, x, a) -> None:
+        """x += a, one fp16 add per element (numel a multiple of 8)."""
+        if x.shape != a.shape: raise RuntimeError("add_f16_: incompatible shapes")
+        self.lib.check(self.lib.exl2_add_f16(self._ptr(x, torch.float16, "x"), self._ptr(a, torch.float16, "a"), x.numel(), self._stream(x)))
+
     def head_norm(self, x, w, b, y, epsilon: float, rms: bool) -> None:
         """ext_norm.cpp:159-200: y = headnorm(x) * w (+ b); x, y half [..., heads, head_dim], w (b) half [heads, head_dim];
         `none_tensor` for b = no bias."""

@@ -12,6 +12,7 @@ from .attn import ExLlamaV2Attention
 from .cache import PAGE_SIZE
 from .config import ExLlamaV2Config
 from .ext import ext_c, none_tensor
+from .layernorm import ExLlamaV2LayerNorm
 from .linear import ExLlamaV2Linear
 from .mlp import ExLlamaV2MLP
 from .moe_mlp import ExLlamaV2MoEMLP
@@ -26,6 +27,11 @@ def rope_tables(cfg: ExLlamaV2Config, device, base: float | None = None):
     freqs = torch.einsum("i,j->ij", t, inv_freq)
     emb = torch.cat((freqs, freqs), dim=-1) if cfg.rope_style == 2 else torch.repeat_interleave(freqs, 2, dim=-1)
     return emb.sin().half().contiguous(), emb.cos().half().contiguous()
+
+
+def _dense_mlp_linears(mlp) -> list:
+    """gate (absent in an ungated MLP), up and down of a dense MLP module"""
+    return [lin for lin in (mlp.gate_proj, mlp.up_proj, mlp.down_proj) if lin is not None]
 
 
 class ExLlamaV2:
@@ -50,6 +56,12 @@ class ExLlamaV2:
         sb = self.ext.paged_attn_scratch_bytes(min(r, 64) * cfg.num_attention_heads, cfg.head_dim, 64)
         self.attn_scratch = torch.empty((sb // 4 + 16,), dtype=torch.float32, device=dev)
         self.attn_counters = torch.zeros((16384,), dtype=torch.int32, device=dev)     # split hand-off tickets (attn.hip)
+        # parallel decoder blocks (Cohere): the two normed copies of the stream the attention and the MLP of a block run in place on
+        self.par_a = self.par_b = None
+        if cfg.parallel_decoder_blocks:
+            self.par_a = torch.empty((r, cfg.hidden_size), dtype=torch.float16, device=dev)
+            self.par_b = torch.empty((r, cfg.hidden_size), dtype=torch.float16, device=dev)
+        self.block_norms = []                             # per layer (weight, bias | None): the .input_layernorm a parallel block owns
         self._dq = None                                   # reconstruct target of ExLlamaV2Linear.forward(force_recons=True)
         self.sin, self.cos = rope_tables(cfg, dev)
         # windowed layers of a model whose local attention has its own rope base (Gemma-3) rotate with a second table
@@ -96,11 +108,17 @@ class ExLlamaV2:
                 mlp = ExLlamaV2MLP(self, key, local_idx).load(ck)
             self.layers.append((attn, mlp))
             self.modules += [attn, mlp]
+            if cfg.parallel_decoder_blocks:
+                self.block_norms.append((ck[key + ".input_layernorm"], ck.get(key + ".input_layernorm.bias")))
         vpad = (cfg.vocab_size + 31) // 32 * 32
         self.vocab_padded = vpad
         if "lm_head" in ck:
-            self.norm = ExLlamaV2RMSNorm(self.ext, "model.norm", self.norm_weight(ck["model.norm"]), cfg.norm_eps)
-            self.lm_head = ExLlamaV2Linear(self.ext, "lm_head", cfg.hidden_size, vpad, self).load(ck["lm_head"])
+            if cfg.layernorm:
+                self.norm = ExLlamaV2LayerNorm(self.ext, "model.norm", ck["model.norm"], ck.get("model.norm.bias"), cfg.norm_eps)
+            else:
+                self.norm = ExLlamaV2RMSNorm(self.ext, "model.norm", self.norm_weight(ck["model.norm"]), cfg.norm_eps)
+            # logit_scale is folded into the head's scales in fp16, as the reference's loader does (model.py:148 -> ext.py:336, :363)
+            self.lm_head = ExLlamaV2Linear(self.ext, "lm_head", cfg.hidden_size, vpad, self).load(ck["lm_head"], prescale=cfg.logit_scale)
         if not self.loaded:
             ExLlamaV2._live_on_device[str(self.device)] = ExLlamaV2._live_on_device.get(str(self.device), 0) + 1
         self.loaded = True
@@ -128,13 +146,15 @@ class ExLlamaV2:
         for attn, mlp in self.layers:
             lins = [attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj]
             if hasattr(mlp, "gate_proj"):
-                lins += [mlp.gate_proj, mlp.up_proj, mlp.down_proj]
+                lins += _dense_mlp_linears(mlp)
             out.update({lin.key: lin for lin in lins})
         return out
 
     def update_loras(self) -> int:
         """model.py:355-364: every module rebuilds its adapter table from what is attached to its linears.  Graphs captured with the
         previous tables must not be replayed afterwards.  Returns the largest rank."""
+        if self.config.layernorm:
+            raise RuntimeError("LoRA adapters are not built for a LayerNorm model (StarCoder2, Cohere)")
         return max([m.update_loras() for m in self.modules if hasattr(m, "update_loras")] + [0])
 
     def weight_bytes(self) -> int:
@@ -145,7 +165,7 @@ class ExLlamaV2:
             for lin in (attn.q_proj, attn.k_proj, attn.v_proj, attn.o_proj):
                 n += lin.weight_bytes()
             if hasattr(mlp, "gate_proj"):
-                n += sum(lin.weight_bytes() for lin in (mlp.gate_proj, mlp.up_proj, mlp.down_proj))
+                n += sum(lin.weight_bytes() for lin in _dense_mlp_linears(mlp))
             else:
                 per_expert = sum(l.weight_bytes() for l in mlp.w1 + mlp.w2 + mlp.w3) // mlp.num_experts
                 n += per_expert * mlp.num_experts_per_token + mlp.gate.numel() * 2
@@ -162,8 +182,15 @@ class ExLlamaV2:
         assert b * q_len <= self.max_rows, "chunk larger than the scratch arena"
         if cfg.residual_fp32:
             return self._forward_chunk_fp32(input_ids, cache, past_len, cache_seqlens, block_table, last_id_only, preprocess_only, loras)
+        if cfg.layernorm and loras:
+            raise RuntimeError("LoRA adapters are not built for a LayerNorm model (StarCoder2, Cohere)")
         x = self.embed_tokens[input_ids.to(self.device).reshape(-1)].view(b, q_len, cfg.hidden_size).contiguous()
-        for attn, mlp in self.layers:
+        if cfg.parallel_decoder_blocks:
+            self._parallel_layers(x, b, q_len, cache, past_len, cache_seqlens, block_table)
+            layers = []
+        else:
+            layers = self.layers
+        for attn, mlp in layers:
             if loras:
                 attn.forward(x, cache, past_len, cache_seqlens, block_table, loras=loras)
                 mlp.forward(x, loras=loras)
@@ -177,6 +204,40 @@ class ExLlamaV2:
         x = self.norm.forward(x)
         logits = self.lm_head.forward(x)
         return logits[..., :cfg.vocab_size]
+
+    def _parallel_layers(self, x, b: int, q_len: int, cache, past_len, cache_seqlens, block_table, final_norm_out=None, bridge: bool = True):
+        """The layers of a model with parallel decoder blocks (parallel_decoder.py:137-143) on the fp16 stream x [b, q_len, hidden], in
+        place: per block n = LN(x), a = attn(n) and m = mlp(n) on two copies of n (handles without norm and residual: they overwrite the
+        rows they are given), x += a, x += m as two fp16 adds in that order.  One launch (ext.parallel_bridge) does the two adds and the
+        next block's norm into both copies; bridge=False, or a shape it declines: add, add, norm, norm as launches of their own --
+        bit-identical.  final_norm_out: the last bridge also leaves the final norm of x there (the decoder's step)."""
+        cfg, ext = self.config, self.ext
+        rows = b * q_len
+        x2 = x.view(rows, cfg.hidden_size)
+        n0, n1 = self.par_a[:rows], self.par_b[:rows]
+
+        def boundary(a, m, w, bias, o0, o1):
+            bias = none_tensor if bias is None else bias
+            if bridge and ext.parallel_bridge(x2, a, m, w, bias, o0, o1, cfg.norm_eps):
+                return
+            if a is not none_tensor:
+                ext.add_f16_(x2, a)
+                ext.add_f16_(x2, m)
+            if w is not none_tensor:
+                ext.layer_norm(x2, w, bias, o0, cfg.norm_eps)
+                if o1 is not none_tensor:
+                    ext.layer_norm(x2, w, bias, o1, cfg.norm_eps)
+
+        boundary(none_tensor, none_tensor, self.block_norms[0][0], self.block_norms[0][1], n0, n1)
+        for i, (attn, mlp) in enumerate(self.layers):
+            attn.forward(n0.view(b, q_len, cfg.hidden_size), cache, past_len, cache_seqlens, block_table)
+            mlp.forward(n1.view(b, q_len, cfg.hidden_size))
+            if i + 1 < len(self.layers):
+                boundary(n0, n1, self.block_norms[i + 1][0], self.block_norms[i + 1][1], n0, n1)
+            elif final_norm_out is not None:
+                boundary(n0, n1, self.norm.weight, self.norm.bias, final_norm_out, none_tensor)
+            else:
+                boundary(n0, n1, none_tensor, None, none_tensor, none_tensor)
 
     def embed_scale(self) -> float:
         cfg = self.config
@@ -285,6 +346,12 @@ class GreedyGraphDecoder:
         self.ids = torch.zeros((batch_size,), dtype=torch.int32, device=dev)
         self.history = torch.zeros((batch_size, cache.max_seq_len + 2), dtype=torch.int32, device=dev)
         self.fp32 = bool(cfg.residual_fp32)
+        # a LayerNorm model decodes module by module (the chained kernels publish sums of squares for an RMS consumer); parallel blocks:
+        # one ext.parallel_bridge launch per block boundary, EXL2_PARALLEL_BRIDGE=0: the separate launches (A/B runs, the identity test)
+        self.layernorm = bool(cfg.layernorm)
+        self.parallel_bridge = bool(cfg.parallel_decoder_blocks) and os.environ.get("EXL2_PARALLEL_BRIDGE", "1") != "0"
+        if self.layernorm and self.loras:
+            raise RuntimeError("LoRA adapters are not built for a LayerNorm model (StarCoder2, Cohere)")
         if self.fp32 and self.loras:
             raise RuntimeError("LoRA adapters are not built for a model with an fp32 residual stream")
         model.check_cache(cache)
@@ -300,7 +367,7 @@ class GreedyGraphDecoder:
         self.chain = None
         self.pos = 0                  # host mirror of cache_seqlens (all rows advance together): bounds are checked here,
         self.limit = min(cache.max_seq_len, cfg.max_seq_len)      # the kernels index pages / sin-cos rows unchecked
-        if os.environ.get("EXL2_CHAIN", "1") != "0" and not self.loras and not self.fp32:
+        if os.environ.get("EXL2_CHAIN", "1") != "0" and not self.loras and not self.fp32 and not self.layernorm:
             self._setup_chain()
         if os.environ.get("EXL2_CHAIN_OVERLAP", "0") != "0" and (self.chain is None or "flags" not in self.chain):
             raise RuntimeError("EXL2_CHAIN_OVERLAP=1 asked for the experimental overlapped chain, but this model / cache / batch is "
@@ -552,6 +619,8 @@ class GreedyGraphDecoder:
         m, ext, cfg = self.model, self.model.ext, self.model.config
         if self.fp32:
             return self._launch_step_fp32()
+        if self.layernorm:
+            return self._launch_step_layernorm()
         ext.embed_rows(m.embed_tokens, self.ids, self.x.view(self.b, cfg.hidden_size))
         for attn, mlp in m.layers:
             if self.loras:
@@ -562,6 +631,24 @@ class GreedyGraphDecoder:
             mlp.forward(self.x)
         ext.rms_norm(self.x.view(self.b, -1), m.norm.weight, self.xn.view(self.b, -1), cfg.norm_eps)
         ext.gemm_half_q_half(self.xn.view(self.b, -1), m.lm_head.q_handle, self.logits)
+        self._select_token()
+
+    def _launch_step_layernorm(self):
+        """The step of a LayerNorm model, module by module.  Sequential blocks (StarCoder2): the handles' own norms.  Parallel blocks
+        (Cohere): the attention in place on one normed copy, the MLP on the other, one bridge launch per block -- the last one leaves the
+        final norm in xn."""
+        m, ext, cfg, b = self.model, self.model.ext, self.model.config, self.b
+        x2 = self.x.view(b, cfg.hidden_size)
+        xn = self.xn.view(b, cfg.hidden_size)
+        ext.embed_rows(m.embed_tokens, self.ids, x2)
+        if cfg.parallel_decoder_blocks:
+            m._parallel_layers(self.x, b, 1, self.cache, 0, self.cache_seqlens, self.block_table, final_norm_out=xn, bridge=self.parallel_bridge)
+        else:
+            for attn, mlp in m.layers:
+                attn.forward(self.x, self.cache, 0, self.cache_seqlens, self.block_table)
+                mlp.forward(self.x)
+            ext.layer_norm(x2, m.norm.weight, none_tensor if m.norm.bias is None else m.norm.bias, xn, cfg.norm_eps)
+        ext.gemm_half_q_half(xn, m.lm_head.q_handle, self.logits)
         self._select_token()
 
     def _launch_step_fp32(self):

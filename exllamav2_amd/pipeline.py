@@ -44,6 +44,8 @@ class PipelineStage:
                  seed: int = 0, ext=None, use_graph: bool = True, cache_type: str = "fp16", depth: int = 1, loras=None):
         if loras:
             raise RuntimeError("pipeline stage: LoRA adapters are not built for the layer split yet")
+        if getattr(cfg, "norm", "rmsnorm") == "layernorm":
+            raise RuntimeError("pipeline stage: a LayerNorm model (StarCoder2, Cohere) is not built for the layer split")
         if getattr(cfg, "residual_fp32", False):
             raise RuntimeError("pipeline stage: a model with an fp32 residual stream (Gemma-2 / Gemma-3) is not built for the layer split")
         assert depth in (1, 2) and (depth == 1 or n_seqs % 2 == 0), "depth 2 needs an even number of sequences"

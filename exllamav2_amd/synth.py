@@ -217,7 +217,8 @@ def synth_checkpoint(cfg, device, recipe: str = "4.0bpw", seed: int = 0, act_ord
         else:
             ck[f"{p}.mlp.up_proj"] = make(h, inter, rec["up_proj"], device, gen, s_attn, act_order)
             ip = shared_of(ck[f"{p}.mlp.up_proj"]) if (shared_perm and act_order) else None
-            ck[f"{p}.mlp.gate_proj"] = make(h, inter, rec["gate_proj"], device, gen, s_attn, act_order, ip)
+            if getattr(cfg, "mlp_gate", True):
+                ck[f"{p}.mlp.gate_proj"] = make(h, inter, rec["gate_proj"], device, gen, s_attn, act_order, ip)
             # the reference folds down_proj's act-order into gate/up at load -> identity perm here
             # (down_act_order=True keeps down_proj's own permutation, as on disk: the reference's loader does the folding)
             ck[f"{p}.mlp.down_proj"] = make(inter, h, rec["down_proj"], device, gen, 0.5 / math.sqrt(inter), down_act_order and act_order)
@@ -234,6 +235,23 @@ def synth_checkpoint(cfg, device, recipe: str = "4.0bpw", seed: int = 0, act_ord
             for nk in ("input_layernorm", "post_attention_layernorm", "pre_feedforward_layernorm", "post_feedforward_layernorm"):
                 if f"{p}.{nk}" in ck:
                     ck[f"{p}.{nk}"] = ck[f"{p}.{nk}"] - cfg.norm_constant_bias
+        if getattr(cfg, "parallel_decoder_blocks", False):
+            del ck[f"{p}.post_attention_layernorm"]                      # one norm per block (architecture.py:715-716: "norm_2": None)
+        gen_b = None                                                     # biases: a generator of their own, as the optional norms above
+        if getattr(cfg, "norm_bias", False):
+            gen_b = gen_b or gen_for(800000 + i)
+            for nk in ("input_layernorm", "post_attention_layernorm"):
+                if f"{p}.{nk}" in ck:
+                    ck[f"{p}.{nk}.bias"] = (0.1 * torch.randn(h, device=device, generator=gen_b)).half()
+        for flag, names in (("attention_bias_qkv", ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")),
+                            ("attention_bias_o", ("self_attn.o_proj",)), ("mlp_bias", ("mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"))):
+            if getattr(cfg, flag, False):
+                gen_b = gen_b or gen_for(800000 + i)
+                for name in names:
+                    if f"{p}.{name}" in ck:
+                        width = {"self_attn.q_proj": qd, "self_attn.k_proj": kvd, "self_attn.v_proj": kvd, "self_attn.o_proj": h,
+                                 "mlp.gate_proj": inter, "mlp.up_proj": inter, "mlp.down_proj": h}[name]
+                        ck[f"{p}.{name}"]["bias"] = (0.1 * torch.randn(width, device=device, generator=gen_b)).half()
         if getattr(cfg, "use_qk_norm", False):
             # per-head q / k norm weights, every head its own row.  A generator of their own: the layer's other tensors are the
             # same draws with and without the norm
@@ -250,6 +268,8 @@ def synth_checkpoint(cfg, device, recipe: str = "4.0bpw", seed: int = 0, act_ord
         ck["model.norm"] = (1 + 0.1 * torch.randn(h, device=device, generator=gen)).half()
         if getattr(cfg, "norm_constant_bias", 0.0):
             ck["model.norm"] = ck["model.norm"] - cfg.norm_constant_bias
+        if getattr(cfg, "norm_bias", False):
+            ck["model.norm.bias"] = (0.1 * torch.randn(h, device=device, generator=gen_for(899991))).half()
         vpad = (cfg.vocab_size + 31) // 32 * 32                               # linear.py:82-88 pads out_features to x32
         ck["lm_head"] = make(h, vpad, rec["lm_head"], device, gen, s_attn, act_order)
         if structured_head:

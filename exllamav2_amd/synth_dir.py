@@ -22,6 +22,8 @@ def write_model_dir(path: str, cfg, ck: dict) -> str:
             for name in ("q_weight", "q_invperm", "q_scale", "q_scale_max", "q_groups", "bias"):
                 if name in v:
                     tensors[f"{key}.{name}"] = v[name].detach().cpu().contiguous()
+        elif key.endswith(".bias"):
+            tensors[key] = v.detach().cpu().contiguous()                  # a LayerNorm's bias sits next to its weight
         else:
             tensors[f"{key}.weight"] = v.detach().cpu().contiguous()
     save_file(tensors, os.path.join(path, "model.safetensors"))
@@ -51,6 +53,25 @@ def write_model_dir(path: str, cfg, ck: dict) -> str:
                        "final_logit_softcapping": cfg.final_logit_softcapping or None,
                        "query_pre_attn_scalar": cfg.query_pre_attn_scalar or cfg.head_dim,
                        "sliding_window": cfg.sliding_window})
+    if getattr(cfg, "norm", "rmsnorm") == "layernorm":
+        # the reference's tensor names (architecture.py:656-676, :704-721): StarCoder2's MLP is .mlp.c_fc / .mlp.c_proj, Cohere has a single
+        # .input_layernorm per block; the quantized lm_head is found under its own key before the tied-embedding alternative
+        del config["rms_norm_eps"]
+        if cfg.parallel_decoder_blocks:
+            if cfg.norm_bias or not cfg.mlp_gate or cfg.rope_style != 1:
+                raise NotImplementedError("write_model_dir: a parallel LayerNorm config is written in the Cohere form only")
+            config.update({"architectures": ["CohereForCausalLM"], "model_type": "cohere", "layer_norm_eps": cfg.norm_eps,
+                           "logit_scale": cfg.logit_scale, "use_qk_norm": bool(cfg.use_qk_norm)})
+        else:
+            if cfg.mlp_gate or not (cfg.norm_bias and cfg.attention_bias_qkv and cfg.attention_bias_o and cfg.mlp_bias) or cfg.rope_style != 2:
+                raise NotImplementedError("write_model_dir: a sequential LayerNorm config is written in the StarCoder2 form only")
+            config.update({"architectures": ["Starcoder2ForCausalLM"], "model_type": "starcoder2", "layer_norm_epsilon": cfg.norm_eps,
+                           "hidden_act": "gelu_pytorch_tanh", "use_bias": True})
+            for key in list(tensors):
+                for ours, theirs in ((".mlp.up_proj.", ".mlp.c_fc."), (".mlp.down_proj.", ".mlp.c_proj.")):
+                    if ours in key:
+                        tensors[key.replace(ours, theirs)] = tensors.pop(key)
+            save_file(tensors, os.path.join(path, "model.safetensors"))
     with open(os.path.join(path, "config.json"), "w") as f:
         json.dump(config, f)
     return path

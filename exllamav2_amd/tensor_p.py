@@ -327,6 +327,8 @@ class ExLlamaV2TP(ExLlamaV2):
     def __init__(self, config, rank: int, world: int, device="cuda:0", ext=None, group=None):
         if getattr(config, "num_experts", 0):
             raise RuntimeError("tensor parallel: MoE blocks are not split (architecture.py:291-305 has no supports_tp)")
+        if getattr(config, "norm", "rmsnorm") == "layernorm":
+            raise RuntimeError("tensor parallel: a LayerNorm model (StarCoder2, Cohere) is not built for the split modules")
         if getattr(config, "residual_fp32", False):
             raise RuntimeError("tensor parallel: a model with an fp32 residual stream (Gemma-2 / Gemma-3) is not built for the split modules")
         max_rows = config.max_input_len * max(1, config.max_batch_size)

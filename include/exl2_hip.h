@@ -487,6 +487,20 @@ int exl2_embed_rows_f32(const void* table, const int* ids, void* out, int rows, 
    fits in a workgroup's registers): nothing was launched and the caller issues the two launches. */
 int exl2_norm_bridge(const void* t, void* x, const void* w_post, const void* w_next, void* n, float epsilon, int rows, int dim,
                      void* stream);
+/* layer_norm / layer_norm_ (ext_norm.cpp -> layer_norm.cu; csrc/layer_norm.hip): y fp16 [rows, dim] = LayerNorm(x fp16) * w (+ b, fp16
+   add) (+ the old y, fp16 add, with add_residual).  b nullable; y may alias x.  Inputs clamped to +-65504, fp32 mean, variance from the
+   squared centred values, (x - mean) * w * rsvar rounded to nearest fp16.  dim: a multiple of 8 up to 16384; any other shape is
+   EXL2_E_UNSUPPORTED ("shape not covered"), nothing is touched. */
+int exl2_layer_norm(const void* x, const void* w, const void* b, void* y, float epsilon, int rows, int dim, int add_residual,
+                    void* stream);
+/* The tail of a parallel decoder block and the head of the next one in one launch (parallel_decoder.py:137-143): x fp16 [rows, dim]
+   += a, += b (two fp16 adds in that order; a and b both null: x is only read), then n0 (and n1 unless null) = exl2_layer_norm of the
+   new x with w (+ bias), bit for bit; w null: the adds only.  n0 may alias a and n1 may alias b.  Returns 0, or 1 = "not covered" for
+   a dim exl2_layer_norm does not cover: nothing was launched, nothing is touched. */
+int exl2_parallel_bridge(void* x, const void* a, const void* b, const void* w, const void* bias, void* n0, void* n1, float epsilon,
+                         int rows, int dim, void* stream);
+/* x fp16 += a over numel elements (a multiple of 8), one fp16 add each: a parallel block's adds as launches of their own. */
+int exl2_add_f16(void* x, const void* a, long long numel, void* stream);
 /* softcap_ (ext_element.cpp:28-50 -> softcap.cu:8-64): x = cap * tanhf(x / cap) in place over exactly numel elements, fp32 (is_fp32 = 1)
    or fp16 through fp32 with round-to-nearest; any numel (the reference's fp16 launch mishandles an odd one). */
 int exl2_softcap(void* x, long long numel, float cap, int is_fp32, void* stream);

@@ -179,5 +179,9 @@ if __name__ == "__main__":
         # a synthetic Gemma-2 directory (exllamav2_amd/synth_dir.py): fp32 residual stream, post norms, soft caps; the flash_attn_func
         # route, whose window_size = (W, W) / softcap the shim carries (attn.py:940-977), and a prompt longer than the window
         main(sys.argv[1], sys.argv[2], flash=True, prompt=GEMMA_PROMPT)
+    elif len(sys.argv) > 3 and sys.argv[3] == "layernorm":
+        # a synthetic StarCoder2 or Cohere directory (exllamav2_amd/synth_dir.py): LayerNorm blocks through ext_c.layer_norm and the
+        # LayerNorm / norm-less module handles; Cohere: the reference's ExLlamaV2ParallelDecoder on two clones of the normed rows
+        main(sys.argv[1], sys.argv[2], flash=True, prompt=GEMMA_PROMPT)
     else:
         main(sys.argv[1], sys.argv[2])
