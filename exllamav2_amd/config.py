@@ -20,7 +20,7 @@ class ExLlamaV2Config:
     max_batch_size: int = 1
     max_input_len: int = 2048               # chunk size of forward (config.py:196, model.py:833)
     arch: str = "llama"
-    num_experts: int = 0                    # > 0: Mixtral-style sparse MLP (moe_mlp.py), experts per token below
+    num_experts: int = 0                    # > 0: sparse-MoE MLP (moe_mlp.py; Mixtral: 8, Qwen3-MoE: 128), experts per token below
     num_experts_per_token: int = 2
     use_qk_norm: bool = False               # per-head norm of q / k between the projections and RoPE (architecture.py:446,459,609)
     headnorm_rms: bool = True               # its form: RMS (Qwen3, Gemma3, OLMo2) or LayerNorm over the head (Cohere)
@@ -127,6 +127,26 @@ class ExLlamaV2Config:
                  use_qk_norm=True, arch="qwen3")
         d.update(kw)
         return ExLlamaV2Config(**d)
+
+    # Qwen3-MoE (Qwen3MoeForCausalLM; architecture.py:450-466): Qwen3 attention with q / k head norm, every MLP a sparse-MoE block of 128
+    # experts, 8 per token; intermediate_size is the EXPERTS' width, as the reference reads moe_intermediate_size into it (config.py:326).
+    # The hyper-parameters are written from memory of the published configs and could not be checked against them where this was
+    # written -- check them against the checkpoint's config.json before relying on them (nothing in the test-suite depends on them
+    # beyond the widths of tests/test_moe_wide_widths.py).
+    @staticmethod
+    def _qwen3_moe(**d):
+        base = dict(num_key_value_heads=4, head_dim=128, vocab_size=151936, norm_eps=1e-6, rotary_embedding_base=1e6, use_qk_norm=True,
+                    num_experts=128, num_experts_per_token=8, arch="qwen3_moe")
+        base.update(d)
+        return ExLlamaV2Config(**base)
+
+    @staticmethod
+    def qwen3_30b_a3b(**kw):
+        return ExLlamaV2Config._qwen3_moe(**(dict(hidden_size=2048, intermediate_size=768, num_hidden_layers=48, num_attention_heads=32) | kw))
+
+    @staticmethod
+    def qwen3_235b_a22b(**kw):
+        return ExLlamaV2Config._qwen3_moe(**(dict(hidden_size=4096, intermediate_size=1536, num_hidden_layers=94, num_attention_heads=64) | kw))
 
     @staticmethod
     def _gemma2(**d):

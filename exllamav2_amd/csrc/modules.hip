@@ -138,7 +138,7 @@ struct QMoEMLP
 {
     const f16* layernorm; float norm_epsilon;
     const f16* gate; int num_experts, num_experts_per_token;
-    QMatrix* w1[MOE_MAX_EXPERTS]; QMatrix* w2[MOE_MAX_EXPERTS]; QMatrix* w3[MOE_MAX_EXPERTS];
+    QMatrix** w1; QMatrix** w2; QMatrix** w3;       // [num_experts] each (one allocation, w1 owns it)
     f16* temp_state; f16* temp_a; f16* temp_b; f16* temp_logits;
     int max_rows, hidden; bool act_gelu;
     bool group_ok;                              // every expert's w1 / w3 share one act-order permutation: grouped launches
@@ -147,6 +147,12 @@ struct QMoEMLP
     bool lean_ok; LeanGroupPlan lean_gu, lean_dn;
     bool lean_rows_ok[LEAN_MAX_M + 1]; LeanGroupPlan lean_gu_r[LEAN_MAX_M + 1], lean_dn_r[LEAN_MAX_M + 1];      // 2-4 rows: one launch over all experts each (the reference's fused form covers <= 4 rows, q_mlp.cu:316-436)
     bool lean_sum_ok; LeanGroupPlan lean_dn2;      // top-2: both selected experts' down projections as ONE pair launch that adds the weighted sum to x (no combine launch)
+    // 64 / 128 experts: pair jobs (moe.h: MoeWide) -- job j = r * topk + y runs the y-th selected expert of row r as a ONE-row launch unit
+    // with its own activation slot (j * inter), partial-output slot (j * hidden) and routing-weight pointer; every expert's one-row
+    // blocks are planned at load time, the select kernel of a pass hands the selected ones out.  Scratch: the host's buffers where
+    // they hold a pass (MOE_WIDE_MAX_JOBS jobs), else the handle's own (wide_own, allocated once here)
+    bool wide_ok; LeanGroupPlan wide_gu, wide_dn;
+    f16* wide_xg; f16* wide_act; f16* wide_part; int* wide_sel_e; f16* wide_sel_w; void* wide_own[5];
 };
 
 // ---- small kernels of the grouped MoE path -----------------------------------------------------------------------------------
@@ -208,6 +214,79 @@ KERNEL void __launch_bounds__(256) moe_combine_kernel(f16* x, const f16* part, c
             {
                 #pragma unroll
                 for (int k = 0; k < 8; k++) acc[k] += (float)pv[e][k];
+            }
+        }
+        #pragma unroll
+        for (int k = 0; k < 8; k++) xv[k] = (f16)acc[k];
+        ((f16x8*)(x + (size_t)row * hidden))[o] = xv;
+        if (co.xp)
+        {
+            #pragma unroll
+            for (int k = 0; k < 8; k++)
+            {
+                const float f = fmaxf(-65504.0f, fminf((float)xv[k], 65504.0f));
+                const f16 yw = co.w ? (f16)fmaxf(-65504.0f, fminf(f * (float)wn[k], 65504.0f)) : xv[k];
+                f16* const dst = co.tiled ? co.xp + ((size_t)(xi[k] >> 3) * 16 + row) * 8 + (xi[k] & 7) : co.xp + (size_t)row * co.ldxp + xi[k];
+                *dst = yw;
+                sq = fmaf(f, f, sq);
+            }
+        }
+    }
+    if (co.xp && co.ss)
+    {
+        sq = wave_allreduce_add(sq);
+        if (lane_id() == 0) sq_part[wave_id()] = sq;
+        block_sync();
+        if (tid() == 0) co.ss[(size_t)row * gdim_x() + bid_x()] = sq_part[0] + sq_part[1] + sq_part[2] + sq_part[3];
+    }
+}
+
+// the same for pair jobs (64 / 128 experts): row r's partial outputs are its topk job slots part[(r * topk + y), :], y in ascending
+// expert order (sel_w: the jobs' routing weights -- a job whose weight is zero is not added, as above); fp32 sum, one rounding into x,
+// the hand-off published exactly as above
+KERNEL void __launch_bounds__(256) moe_combine_jobs_kernel(f16* x, const f16* part, const f16* sel_w, int rows, int hidden, int topk, const MoeChainOut co)
+{
+    SHARED float sq_part[4];
+    const int row = bid_y();
+    const int o = bid_x() * 256 + tid();
+    const bool on = o * 8 < hidden;
+    float sq = 0.0f;
+    if (on)
+    {
+        f16x8 xv = ((const f16x8*)(x + (size_t)row * hidden))[o];
+        u32 mask = 0;
+        #pragma unroll
+        for (int y = 0; y < MOE_MAX_SEL; y++) if (y < topk && as_u16(sel_w[(size_t)row * topk + y]) != 0) mask |= 1u << y;
+        u32 xi[8];
+        const bool vec_perm = co.xp && co.invperm && (((size_t)co.invperm) & 15) == 0;
+        if (vec_perm)
+        {
+            const u32x4 pv = ((const u32x4*)co.invperm)[o];
+            xi[0] = pv.x & 0xFFFFu; xi[1] = pv.x >> 16; xi[2] = pv.y & 0xFFFFu; xi[3] = pv.y >> 16;
+            xi[4] = pv.z & 0xFFFFu; xi[5] = pv.z >> 16; xi[6] = pv.w & 0xFFFFu; xi[7] = pv.w >> 16;
+        }
+        else
+        {
+            #pragma unroll
+            for (int k = 0; k < 8; k++) xi[k] = (co.xp && co.invperm) ? (u32)co.invperm[o * 8 + k] : (u32)(o * 8 + k);
+        }
+        const f16x8 z8 = {(f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f};
+        f16x8 pv[MOE_MAX_SEL];
+        #pragma unroll
+        for (int y = 0; y < MOE_MAX_SEL; y++) pv[y] = ((mask >> y) & 1u) ? ((const f16x8*)(part + ((size_t)row * topk + y) * hidden))[o] : z8;
+        f16 wn[8];
+        #pragma unroll
+        for (int k = 0; k < 8; k++) wn[k] = (co.xp && co.w) ? co.w[xi[k]] : (f16)1.0f;
+        float acc[8];
+        #pragma unroll
+        for (int k = 0; k < 8; k++) acc[k] = (float)xv[k];
+        #pragma unroll
+        for (int y = 0; y < MOE_MAX_SEL; y++)
+        {
+            if ((mask >> y) & 1u)
+            {
+                #pragma unroll
+                for (int k = 0; k < 8; k++) acc[k] += (float)pv[y][k];
             }
         }
         #pragma unroll
@@ -394,6 +473,65 @@ static void moe_plan_lean(QMoEMLP* m)
     }
 }
 
+static void moe_free_wide(QMoEMLP* m)
+{
+    if (m->wide_ok) { qgemv_lean_group_free(&m->wide_gu); qgemv_lean_group_free(&m->wide_dn); }
+    m->wide_ok = false;
+    for (int i = 0; i < 5; i++) { if (m->wide_own[i]) (void)hipFree(m->wide_own[i]); m->wide_own[i] = nullptr; }
+}
+
+// the pair-job route's plans (64 / 128 experts): every expert's gate|up pair and down projection as ONE-row blocks; the pointers a
+// job gets of its own (input row, activation slot, partial-output slot, routing weight) are patched in by the select kernel of a pass
+static void moe_plan_wide(QMoEMLP* m)
+{
+    m->wide_ok = false;
+    const int E = m->num_experts, topk = m->num_experts_per_token, hidden = m->hidden, inter = m->w1[0]->width;
+    if (!moe_wide_experts(E) || topk > MOE_MAX_SEL || !hidden_ok(m) || (inter & 7) || getenv("EXL2_MOE_NO_LEAN_PLAN")) return;
+    {
+        std::vector<QMatrix*> all((size_t)2 * E);
+        for (int i = 0; i < E; i++) { all[2 * i] = m->w1[i]; all[2 * i + 1] = m->w3[i]; }
+        if (!same_perm(all.data(), 2 * E)) return;
+    }
+    const int jobs = MOE_WIDE_MAX_ROWS * topk;
+    auto own = [&](int slot, size_t bytes) -> void* {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        const std::vector<u8> zero(bytes, 0);
+        if (hipMemcpy(p, zero.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return nullptr; }
+        m->wide_own[slot] = p;
+        return p;
+    };
+    // what the host's buffers hold of a pass is taken from them (temp_a / temp_b: [max_rows, inter]); the rows in the experts' packed
+    // order are the handle's own (temp_state holds the normalised rows of EVERY pass)
+    m->wide_xg = (f16*)own(0, (size_t)MOE_WIDE_MAX_ROWS * hidden * 2);
+    m->wide_act = jobs <= m->max_rows ? m->temp_a : (f16*)own(1, (size_t)jobs * inter * 2);
+    m->wide_part = (long long)jobs * hidden <= (long long)m->max_rows * inter ? m->temp_b : (f16*)own(2, (size_t)jobs * hidden * 2);
+    m->wide_sel_e = (int*)own(3, (size_t)jobs * sizeof(int));
+    m->wide_sel_w = (f16*)own(4, (size_t)jobs * 2);
+    if (!m->wide_xg || !m->wide_act || !m->wide_part || !m->wide_sel_e || !m->wide_sel_w) { moe_free_wide(m); return; }
+    std::vector<FlatIn> ins((size_t)E);
+    for (int e = 0; e < E; e++)
+    {
+        FlatIn& in = ins[e]; memset(&in, 0, sizeof(in));
+        in.qm[0] = m->w1[e]; in.qm[1] = m->w3[e];
+        in.c[0] = m->wide_act; in.c[1] = in.c[0]; in.ldc[0] = inter; in.ldc[1] = inter;
+        in.c_invperm[0] = m->w2[e]->q_perm ? m->w2[e]->q_invperm : nullptr;
+        in.n_mats = 2; in.pair = 1; in.M = 1; in.a_mode = A_DIRECT; in.a = m->wide_xg; in.lda = hidden; in.c_mode = C_STORE;
+        in.act_gelu = m->act_gelu ? 1 : 0;
+    }
+    if (qgemv_lean_group_plan(ins.data(), E, nullptr, topk, &m->wide_gu, 0, 1, jobs) != 0) { moe_free_wide(m); return; }
+    std::vector<const f16*> scale((size_t)E);
+    for (int e = 0; e < E; e++)
+    {
+        FlatIn& in = ins[e]; memset(&in, 0, sizeof(in));
+        in.qm[0] = m->w2[e]; in.c[0] = m->wide_part; in.ldc[0] = hidden;
+        in.n_mats = 1; in.M = 1; in.a_mode = A_DIRECT; in.a = m->wide_act; in.lda = inter; in.c_mode = C_STORE;
+        scale[e] = m->temp_logits + e;
+    }
+    if (qgemv_lean_group_plan(ins.data(), E, scale.data(), topk, &m->wide_dn, 0, 1, jobs) != 0) { qgemv_lean_group_free(&m->wide_gu); moe_free_wide(m); return; }
+    m->wide_ok = true;
+}
+
 int exl2_make_q_moe_mlp(void** handle, const void* layernorm, const void* layernorm_bias, int layernorm_is_rms,
                         float norm_epsilon, const void* gate, int num_experts, int num_experts_per_token,
                         void* const* w1, void* const* w2, void* const* w3, void* temp_state, void* temp_gathered_state,
@@ -402,18 +540,22 @@ int exl2_make_q_moe_mlp(void** handle, const void* layernorm, const void* layern
     (void)temp_gathered_state; (void)temp_dq; (void)layernorm_bias;
     EXL2_REQUIRE(handle && gate && w1 && w2 && w3, "make_q_moe_mlp: null argument");
     EXL2_REQUIRE(layernorm && layernorm_is_rms, "make_q_moe_mlp: only RMSNorm pre-norm is built (a LayerNorm MoE block is not)");
-    EXL2_REQUIRE(num_experts == 4 || num_experts == 8 || num_experts == 16,
-                 "make_q_moe_mlp: %d experts (the fused path covers 4, 8, 16 like q_mlp.cu:333)", num_experts);
+    EXL2_REQUIRE(num_experts == 4 || num_experts == 8 || num_experts == 16 || moe_wide_experts(num_experts),
+                 "make_q_moe_mlp: %d experts (the fused path covers 4, 8, 16 like q_mlp.cu:333, and 64, 128)", num_experts);
     EXL2_REQUIRE(num_experts_per_token >= 1 && num_experts_per_token <= num_experts, "make_q_moe_mlp: bad experts per token");
+    EXL2_REQUIRE(!moe_wide_experts(num_experts) || num_experts_per_token <= MOE_MAX_SEL, "make_q_moe_mlp: %d experts take at most %d per token", num_experts, MOE_MAX_SEL);
     EXL2_REQUIRE(temp_state && temp_a && temp_b && temp_logits, "make_q_moe_mlp: temp buffers required");
     QMoEMLP* m = (QMoEMLP*)calloc(1, sizeof(QMoEMLP));
     if (!m) EXL2_FAIL(EXL2_E_OOM, "make_q_moe_mlp: host out of memory");
     m->layernorm = (const f16*)layernorm; m->norm_epsilon = norm_epsilon; m->gate = (const f16*)gate;
     m->num_experts = num_experts; m->num_experts_per_token = num_experts_per_token;
+    m->w1 = (QMatrix**)calloc((size_t)3 * num_experts, sizeof(QMatrix*));
+    if (!m->w1) { free(m); EXL2_FAIL(EXL2_E_OOM, "make_q_moe_mlp: host out of memory"); }
+    m->w2 = m->w1 + num_experts; m->w3 = m->w2 + num_experts;
     for (int i = 0; i < num_experts; i++)
     {
         m->w1[i] = (QMatrix*)w1[i]; m->w2[i] = (QMatrix*)w2[i]; m->w3[i] = (QMatrix*)w3[i];
-        if (!m->w1[i] || !m->w2[i] || !m->w3[i]) { free(m); EXL2_FAIL(EXL2_E_INVALID, "make_q_moe_mlp: expert %d has a null projection", i); }
+        if (!m->w1[i] || !m->w2[i] || !m->w3[i]) { free(m->w1); free(m); EXL2_FAIL(EXL2_E_INVALID, "make_q_moe_mlp: expert %d has a null projection", i); }
     }
     m->temp_state = (f16*)temp_state; m->temp_a = (f16*)temp_a; m->temp_b = (f16*)temp_b; m->temp_logits = (f16*)temp_logits;
     m->max_rows = max_rows; m->hidden = m->w1[0]->height; m->act_gelu = act_gelu;
@@ -421,10 +563,11 @@ int exl2_make_q_moe_mlp(void** handle, const void* layernorm, const void* layern
         // grouped launches (qgemv_flat.hip) need one packed input order for every expert's gate / up projection -- the
         // quantizer gives them one (conversion/quantize.py:190-192: w1.i and w3.i reuse w1.0's Hessian)
         QMatrix* all[2 * MOE_MAX_EXPERTS];
-        for (int i = 0; i < num_experts; i++) { all[2 * i] = m->w1[i]; all[2 * i + 1] = m->w3[i]; }
-        m->group_ok = num_experts <= 16 && same_perm(all, 2 * num_experts) && hidden_ok(m);
+        for (int i = 0; i < num_experts && i < MOE_MAX_EXPERTS; i++) { all[2 * i] = m->w1[i]; all[2 * i + 1] = m->w3[i]; }
+        m->group_ok = num_experts <= MOE_MAX_EXPERTS && same_perm(all, 2 * num_experts) && hidden_ok(m);
     }
     moe_plan_lean(m);
+    moe_plan_wide(m);
     *handle = m;
     return EXL2_OK;
 }
@@ -435,6 +578,7 @@ int exl2_free_q_moe_mlp(void* handle)
     if (m && m->lean_ok) { qgemv_lean_group_free(&m->lean_gu); qgemv_lean_group_free(&m->lean_dn); }
     if (m && m->lean_sum_ok) qgemv_lean_group_free(&m->lean_dn2);
     for (int r = 2; m && r <= LEAN_MAX_M; r++) if (m->lean_rows_ok[r]) { qgemv_lean_group_free(&m->lean_gu_r[r]); qgemv_lean_group_free(&m->lean_dn_r[r]); }
+    if (m) { moe_free_wide(m); free(m->w1); }
     free(handle);
     return EXL2_OK;
 }
@@ -458,6 +602,58 @@ static int moe_forward(void* handle, void* x_, int rows, const MoeChainOut& co, 
     f16* const xg = m->temp_state + (size_t)MAX_GEMV_ROWS * hidden;       // normalised rows in the experts' packed order
     const bool xg_room = m->group_ok && rows <= MAX_GEMV_ROWS && 2 * MAX_GEMV_ROWS <= m->max_rows;
     int front = 1;
+    // ---- 64 / 128 experts, pair jobs: per pass of <= 16 rows logits -> select + hand-out -> gate|up (grid.y = jobs) -> down (grid.y =
+    // jobs) -> combine; EXL2_MOE_UNFUSED_FRONT=1: the norm as a launch of its own in front (the same routing, bit for bit)
+    if (m->wide_ok && !ENV_SET("EXL2_MOE_NO_LEAN") && !ENV_SET("EXL2_MOE_SERIAL") && !ENV_SET("EXL2_MOE_NO_GROUP"))
+    {
+        const int topk = m->num_experts_per_token;
+        const bool unfused = ENV_SET("EXL2_MOE_UNFUSED_FRONT");
+        int npart = 0;
+        for (int r0 = 0; r0 < rows; r0 += MOE_WIDE_MAX_ROWS)
+        {
+            const int nr = rows - r0 < MOE_WIDE_MAX_ROWS ? rows - r0 : MOE_WIDE_MAX_ROWS;
+            const int jobs = nr * topk;
+            f16* const xr = x + (size_t)r0 * hidden;
+            f16* const xn = m->temp_state + (size_t)r0 * hidden;
+            f16* const lg = m->temp_logits + (size_t)r0 * E;
+            MoeWide wd; memset(&wd, 0, sizeof(wd));
+            const LeanGroupPlan* const gp[2] = {&m->wide_gu, &m->wide_dn};
+            for (int k = 0; k < 2; k++)
+            {
+                wd.src[k] = (const u32x4*)gp[k]->table_src; wd.dst[k] = (u32x4*)gp[k]->table_sel; wd.units[k] = gp[k]->block_bytes / 16;
+                for (int q = 0; q < MOE_WIDE_PATCHES; q++) wd.patch[k][q].off = -1;
+            }
+            wd.patch[0][0] = {gp[0]->off_a, 0u, (u32)hidden * 2u, 0u, (u64)(size_t)m->wide_xg};
+            wd.patch[0][1] = {gp[0]->off_c[0], (u32)inter * 2u, 0u, 0u, (u64)(size_t)m->wide_act};
+            wd.patch[0][2] = {gp[0]->off_c[1], (u32)inter * 2u, 0u, 0u, (u64)(size_t)m->wide_act};
+            wd.patch[1][0] = {gp[1]->off_a, (u32)inter * 2u, 0u, 0u, (u64)(size_t)m->wide_act};
+            wd.patch[1][1] = {gp[1]->off_c[0], (u32)hidden * 2u, 0u, 0u, (u64)(size_t)m->wide_part};
+            wd.patch[1][2] = {gp[1]->off_scale, 0u, (u32)E * 2u, 2u, (u64)(size_t)lg};
+            wd.sel_e = m->wide_sel_e; wd.sel_w = m->wide_sel_w;
+            if (unfused)
+            {
+                const int rc = exl2_rms_norm(xr, m->layernorm, xn, m->norm_epsilon, nr, hidden, 0, 0, 0, stream);
+                if (rc) return rc;
+                front = moe_wide_front_launch(xn, nullptr, m->gate, m->w1[0]->q_perm, nullptr, m->wide_xg, lg, nr, hidden, E, topk, m->norm_epsilon, &wd, stream);
+            }
+            else
+                front = moe_wide_front_launch(xr, m->layernorm, m->gate, m->w1[0]->q_perm, xn, m->wide_xg, lg, nr, hidden, E, topk, m->norm_epsilon, &wd, stream);
+            if (front < 0) return front;
+            if (front != 0) EXL2_FAIL(EXL2_E_INVALID, "q_moe_mlp_forward_: the planned pair-job front was not taken");
+            if (ENV_SET("EXL2_DEBUG_ROUTE")) fprintf(stderr, "q_moe_mlp route: pairs rows=%d experts=%d jobs=%d\n", nr, E, jobs);
+            if (qgemv_lean_group_launch(&m->wide_gu, stream, nullptr, jobs) != 0 || qgemv_lean_group_launch(&m->wide_dn, stream, nullptr, jobs) != 0)
+                EXL2_FAIL(EXL2_E_INVALID, "q_moe_mlp_forward_: a planned lean launch was not taken");
+            MoeChainOut cr = co;
+            if (cr.xp && !cr.tiled) cr.xp += (size_t)r0 * cr.ldxp;
+            npart = (hidden / 8 + 255) / 256;
+            if (cr.ss) cr.ss += (size_t)r0 * npart;
+            LAUNCH(moe_combine_jobs_kernel, dim3((unsigned)npart, (unsigned)nr, 1), dim3(256), 0, stream,
+                   xr, (const f16*)m->wide_part, (const f16*)m->wide_sel_w, nr, hidden, topk, cr);
+            HIP_TRY(hipGetLastError());
+        }
+        if (npart_out) *npart_out = npart;
+        return EXL2_OK;
+    }
     // ---- one row on the lean kernel: front (+ the selected experts' argument blocks) -> gate|up -> down -> combine
     if (rows == 1 && m->lean_ok && !ENV_SET("EXL2_MOE_NO_LEAN") && !ENV_SET("EXL2_MOE_UNFUSED_FRONT") && !ENV_SET("EXL2_MOE_SERIAL") && !ENV_SET("EXL2_MOE_NO_GROUP"))
     {

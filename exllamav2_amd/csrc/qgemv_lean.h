@@ -20,6 +20,9 @@ struct LeanGroupPlan
     int S, nslots, pair, walk, grid_x; unsigned lds;
     int all_groups;                             // 2-4 rows: one launch over ALL experts' planned blocks (r_stride != 0), no copies
     int pair_sum, b_lo, b_hi, b2_lo, b2_hi;     // FlatIn.pair_sum plans: 16-byte units of a step's block that come from the SECOND selected expert
+    // pair jobs (64 / 128 experts; moe.h: MoeWide): table_sel has sel_slots blocks (>= n_sel), a launch says how many it runs; byte offsets
+    // inside a block of the pointers a job gets of its own -- the activations, the outputs of matrix 0 / 1, the routing weight
+    int sel_slots, off_a, off_c[2], off_scale;
 };
 // what a pair_sum launch takes at launch time: the residual rows the weighted sum is added to (+ the hand-off for the next consumer, nullable)
 struct LeanGroupDyn { void* c; int ldc; void* xp_out; const void* xp_invperm; const void* xp_w; float* ss_out; int ldxp; };
@@ -27,6 +30,8 @@ struct LeanGroupDyn { void* c; int ldc; void* xp_out; const void* xp_invperm; co
 // 1: a shape the lean kernel declines or experts whose plans differ in geometry (the caller keeps its other route)
 // r_stride != 0 (2-4 rows): out_scale[g][row * r_stride] = the group's routing weight of that row; the launch then covers all groups
 // and a group without a routed row leaves at entry.  mul: the finished sums are multiplied by the weight (down projections)
-int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out_scale, int n_sel, LeanGroupPlan* plan, int r_stride = 0, int mul = 1);
-int qgemv_lean_group_launch(const LeanGroupPlan* plan, void* stream, const LeanGroupDyn* dyn = nullptr);
+// sel_slots (pair jobs): blocks of table_sel, 0 = n_sel (which then may exceed n_groups: a job per ROW and selected expert)
+int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out_scale, int n_sel, LeanGroupPlan* plan, int r_stride = 0, int mul = 1, int sel_slots = 0);
+// n_jobs (pair jobs): blocks of table_sel this launch runs (blockIdx.y), 0 = n_sel
+int qgemv_lean_group_launch(const LeanGroupPlan* plan, void* stream, const LeanGroupDyn* dyn = nullptr, int n_jobs = 0);
 void qgemv_lean_group_free(LeanGroupPlan* plan);

@@ -1434,9 +1434,9 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
 
 // ---- grouped-expert launches (qgemv_lean.h) ---------------------------------------------------------------------------------------
 
-int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out_scale, int n_sel, LeanGroupPlan* gp, int r_stride, int mul)
+int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out_scale, int n_sel, LeanGroupPlan* gp, int r_stride, int mul, int sel_slots)
 {
-    if (!ins || !gp || n_groups < 1 || n_sel < 1 || n_sel > n_groups) return 1;
+    if (!ins || !gp || n_groups < 1 || n_sel < 1 || n_sel > n_groups || sel_slots < 0 || (sel_slots && (sel_slots < n_sel || ins[0].pair_sum || r_stride))) return 1;
     memset(gp, 0, sizeof(*gp));
     std::vector<LeanArgs> blocks((size_t)n_groups);
     static LeanExport ex;                                            // (large: off the stack)
@@ -1495,10 +1495,15 @@ int qgemv_lean_group_plan(const FlatIn* ins, int n_groups, const f16* const* out
     gp->b_lo = (int)(offsetof(LeanArgs, mat) + sizeof(LeanMat)) / 16; gp->b_hi = gp->b_lo + (int)sizeof(LeanMat) / 16;
     gp->b2_lo = (int)(offsetof(LeanArgs, wave) + (size_t)gp->S * sizeof(LeanWave)) / 16; gp->b2_hi = gp->b2_lo + gp->S * (int)sizeof(LeanWave) / 16;
     if (hipMalloc(&gp->table_src, (size_t)n_groups * sizeof(LeanArgs)) != hipSuccess) { gp->table_src = nullptr; return 1; }
-    if (hipMalloc(&gp->table_sel, (size_t)n_sel * sizeof(LeanArgs)) != hipSuccess) { (void)hipFree(gp->table_src); gp->table_src = gp->table_sel = nullptr; return 1; }
+    gp->sel_slots = sel_slots ? sel_slots : n_sel;
+    gp->off_a = (int)(offsetof(LeanArgs, hdr) + offsetof(LeanHdr, a)); gp->off_scale = (int)(offsetof(LeanArgs, hdr) + offsetof(LeanHdr, out_scale));
+    for (int j = 0; j < 2; j++) gp->off_c[j] = (int)(offsetof(LeanArgs, mat) + (size_t)j * sizeof(LeanMat) + offsetof(LeanMat, c));
+    if (hipMalloc(&gp->table_sel, (size_t)gp->sel_slots * sizeof(LeanArgs)) != hipSuccess) { (void)hipFree(gp->table_src); gp->table_src = gp->table_sel = nullptr; return 1; }
     if (hipMemcpy(gp->table_src, blocks.data(), (size_t)n_groups * sizeof(LeanArgs), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(gp->table_sel, blocks.data(), (size_t)n_sel * sizeof(LeanArgs), hipMemcpyHostToDevice) != hipSuccess)    // (valid blocks until the first front kernel runs)
     { qgemv_lean_group_free(gp); return 1; }
+    for (int s = n_sel; s < gp->sel_slots; s++)                      // (the further job slots too)
+        if (hipMemcpy((LeanArgs*)gp->table_sel + s, &blocks[(size_t)(s % n_groups)], sizeof(LeanArgs), hipMemcpyHostToDevice) != hipSuccess) { qgemv_lean_group_free(gp); return 1; }
     return 0;
 }
 
@@ -1510,9 +1515,10 @@ void qgemv_lean_group_free(LeanGroupPlan* gp)
     gp->table_src = gp->table_sel = nullptr;
 }
 
-int qgemv_lean_group_launch(const LeanGroupPlan* gp, void* stream, const LeanGroupDyn* dyn_)
+int qgemv_lean_group_launch(const LeanGroupPlan* gp, void* stream, const LeanGroupDyn* dyn_, int n_jobs)
 {
     if (!gp || !gp->table_sel) return 1;
+    if (n_jobs < 0 || n_jobs > gp->sel_slots || (n_jobs && (gp->pair_sum || gp->all_groups))) return 1;
     LeanDyn dyn; memset(&dyn, 0, sizeof(dyn));
     if (dyn_) { dyn.c = (f16*)dyn_->c; dyn.xp_out = (f16*)dyn_->xp_out; dyn.xp_invperm = (const u16*)dyn_->xp_invperm; dyn.xp_w = (const f16*)dyn_->xp_w;
                 dyn.ss_out = dyn_->ss_out; dyn.ldc = dyn_->ldc; dyn.ldxp = dyn_->ldxp; }
@@ -1525,7 +1531,7 @@ int qgemv_lean_group_launch(const LeanGroupPlan* gp, void* stream, const LeanGro
 #undef LEAN_ATTR
     }
     // (all_groups: blockIdx.y = expert, the blocks as planned -- workgroups of experts without a row leave at entry)
-    const dim3 grid((unsigned)gp->grid_x, (unsigned)(gp->pair_sum ? 1 : (gp->all_groups ? gp->n_groups : gp->n_sel)), 1), block((unsigned)(gp->S * gp->nslots) * 64, 1, 1);
+    const dim3 grid((unsigned)gp->grid_x, (unsigned)(gp->pair_sum ? 1 : (gp->all_groups ? gp->n_groups : (n_jobs ? n_jobs : gp->n_sel))), 1), block((unsigned)(gp->S * gp->nslots) * 64, 1, 1);
     const LeanArgs* const table = (const LeanArgs*)(gp->all_groups ? gp->table_src : gp->table_sel);
     const LeanMoeKernelFn kernel = lean_moe_kernel(gp->S, gp->nslots, gp->pair != 0, gp->walk != 0);
     if (!kernel) return 1;

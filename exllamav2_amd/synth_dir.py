@@ -36,7 +36,27 @@ def write_model_dir(path: str, cfg, ck: dict) -> str:
         "hidden_act": "silu", "bos_token_id": 1, "eos_token_id": 2, "pad_token_id": 0, "tie_word_embeddings": False,
         "torch_dtype": "float16",
     }
-    if getattr(cfg, "num_experts", 0):
+    if getattr(cfg, "num_experts", 0) and getattr(cfg, "use_qk_norm", False):
+        # Qwen3-MoE (architecture.py:450-466): .mlp.experts.{e}.gate_proj | up_proj | down_proj (the internal w1 | w3 | w2), the router
+        # .mlp.gate, the head norms .self_attn.q_norm / .k_norm; config.py:322-326 reads num_experts / num_experts_per_tok /
+        # moe_intermediate_size
+        # (the directory does not say which form the head norm has: the reference decides by architecture -- `headnorm = "layernorm"`
+        # unless the architecture sets it, architecture.py:219, and Qwen3 / Qwen3-MoE do not)
+        if getattr(cfg, "residual_fp32", False) or getattr(cfg, "norm", "rmsnorm") == "layernorm":
+            raise NotImplementedError("write_model_dir: a sparse-MoE config with head norm is written in the Qwen3-MoE form only")
+        config.update({"architectures": ["Qwen3MoeForCausalLM"], "model_type": "qwen3_moe", "num_experts": cfg.num_experts,
+                       "num_experts_per_tok": cfg.num_experts_per_token, "moe_intermediate_size": cfg.intermediate_size,
+                       "norm_topk_prob": True})
+        for key in list(tensors):
+            new = key.replace(".block_sparse_moe.gate.", ".mlp.gate.")
+            if ".block_sparse_moe.experts." in new:
+                new = new.replace(".block_sparse_moe.experts.", ".mlp.experts.")
+                for ours, theirs in ((".w1.", ".gate_proj."), (".w3.", ".up_proj."), (".w2.", ".down_proj.")):
+                    new = new.replace(ours, theirs)
+            if new != key:
+                tensors[new] = tensors.pop(key)
+        save_file(tensors, os.path.join(path, "model.safetensors"))
+    elif getattr(cfg, "num_experts", 0):
         # a sparse-MoE checkpoint in the reference's Mixtral form (architecture.py:291-305: block_sparse_moe.gate / experts.*.w1|w2|w3,
         # config.py:322-323: num_local_experts / num_experts_per_tok)
         config.update({"architectures": ["MixtralForCausalLM"], "model_type": "mixtral",

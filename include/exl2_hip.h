@@ -363,7 +363,9 @@ int exl2_lora_group_set_loras(void* handle, int n_loras, const uint64_t* ids, co
 int exl2_apply_loras(void* handle, int n_loras, const uint64_t* ids, const void* x, void* const* out, int rows, void* stream);
 
 /* make_q_moe_mlp / q_moe_mlp_forward_ (ext_qmlp.h, ext_qmlp.cpp:245-272 -> QMoEMLP::forward_ cuda/q_mlp.cu:318-402).
-   w1 / w2 / w3: arrays of num_experts q_matrix handles (gate, down, up projections).  num_experts in {4, 8, 16}.
+   w1 / w2 / w3: arrays of num_experts q_matrix handles (gate, down, up projections).  num_experts in {4, 8, 16} or {64, 128}
+   (Qwen3-MoE; at most 8 experts per token; q_mlp.cu:403-435 leaves the device there, this library does not: the handle owns what
+   scratch of a 16-row pass the temp buffers do not hold, the forward allocates, copies and synchronises nothing).
    The reference accepts rows <= 4; this entry point takes any rows <= max_rows (16-row passes). */
 int exl2_make_q_moe_mlp(void** handle, const void* layernorm, const void* layernorm_bias, int layernorm_is_rms,
                         float norm_epsilon, const void* gate, int num_experts, int num_experts_per_token,
@@ -375,7 +377,8 @@ int exl2_q_moe_mlp_forward(void* handle, void* x, int rows, void* stream);
    rms_norm.cu:33-175): also publishes (xp_out, ss_out with *npart_out partial sums per row) for the next consumer */
 int exl2_q_moe_mlp_forward_chain(void* handle, void* x, int rows, const void* next_invperm, const void* next_norm_w, void* xp_out,
                                  float* ss_out, int* npart_out, void* stream);
-/* router: logits[rows, E] = x gate^T, then softmax -> top-k -> renormalise in place (cuda/q_mlp_softmax.cuh) */
+/* router: logits[rows, E] = x gate^T, then softmax -> top-k -> renormalise in place (cuda/q_mlp_softmax.cuh); E in {4, 8, 16, 64, 128}
+   (64 / 128: top-k <= 8; of equal values at the boundary the higher index is kept, as the reference's drop loop does) */
 int exl2_moe_route(const void* x, const void* gate, void* logits, int rows, int hidden, int num_experts, int topk, void* stream);
 
 /* ---- chained decode (ours; replaces the COMPOSITION q_attn.cu:153-345 / q_mlp.cu:153-236 make of rms_norm + q_gemm +

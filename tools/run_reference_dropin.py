@@ -168,8 +168,49 @@ def main_split(model_dir: str, out: str, steps: int = 4):
     print("reference-on-dropin ok (load(gpu_split), layer split over devices", used, "):", toks)
 
 
+QWEN3_MOE_PROMPT = (169, 280, 85, 245, 202, 3)     # (tests/test_dropin_qwen3_moe.py: every position and the steps behind it have a clear router decision in the oracle)
+
+
+def main_qwen3_moe(model_dir: str, out: str, steps: int = 4):
+    """A synthetic Qwen3-MoE directory (exllamav2_amd/synth_dir.py: Qwen3MoeForCausalLM, 128 experts, top 8): a prompt of six rows (more
+    than 4: the reference's torch loop over the experts, moe_mlp.py:255-323), single-token steps (ext_c.q_moe_mlp_forward_ at one row) and
+    ONE call of three sequences at one token each on a cache of their own (three rows through ext_c.q_moe_mlp_forward_: the rows the
+    reference's own kernel gets wrong, q_mlp.cu:403-435 copies only row 0's weights)."""
+    from exllamav2 import ExLlamaV2, ExLlamaV2Config, ExLlamaV2Cache
+    from exllamav2.ext import ext_c
+    assert ext_c.__name__ == "exllamav2_ext" and "dropin" in ext_c.__file__, ext_c.__file__
+    config = ExLlamaV2Config(model_dir)
+    assert config.arch.lm.is_moe and config.num_experts == 128, (config.num_experts,)
+    config.max_seq_len = 256
+    config.max_input_len = 32
+    config.max_batch_size = 3
+    config.no_flash_attn = True
+    config.no_sdpa = True
+    model = ExLlamaV2(config)
+    model.load()
+    cache = ExLlamaV2Cache(model, max_seq_len=256)
+    ids = torch.tensor([list(QWEN3_MOE_PROMPT)])
+    logits = model.forward(ids, cache, last_id_only=False)
+    all_logits = [logits.float().cpu().numpy()]
+    toks = []
+    for _ in range(steps):
+        sample = torch.argmax(logits[0, -1]).cpu().unsqueeze(0).unsqueeze(0)
+        toks.append(int(sample))
+        ids = torch.cat((ids, sample), dim=-1)
+        logits = model.forward(ids[:, -1:], cache)
+        all_logits.append(logits.float().cpu().numpy())
+    cache3 = ExLlamaV2Cache(model, batch_size=3, max_seq_len=256)
+    ids3 = torch.tensor([[3], [7], [11]])
+    logits3 = model.forward(ids3, cache3)
+    np.savez(out, prefill=all_logits[0], steps=np.concatenate(all_logits[1:], axis=1), tokens=np.array(toks),
+             batch3_ids=ids3.numpy(), batch3=logits3.float().cpu().numpy())
+    print("reference-on-dropin ok (Qwen3-MoE: torch loop, one-row steps, one three-row call):", toks)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 3 and sys.argv[3] == "tp":
+    if len(sys.argv) > 3 and sys.argv[3] == "qwen3_moe":
+        main_qwen3_moe(sys.argv[1], sys.argv[2])
+    elif len(sys.argv) > 3 and sys.argv[3] == "tp":
         main_tp(sys.argv[1], sys.argv[2])
     elif len(sys.argv) > 3 and sys.argv[3] == "split":
         main_split(sys.argv[1], sys.argv[2])
