@@ -8,6 +8,7 @@ module interface needed to drive it.
 from .ext import ext_c, none_tensor, ExtC  # noqa: F401
 from .config import ExLlamaV2Config  # noqa: F401
 from .model import ExLlamaV2, GreedyGraphDecoder  # noqa: F401
+from .speculative import SpeculativeGraphDecoder  # noqa: F401
 from .lora import ExLlamaV2Lora  # noqa: F401
 from .cache import ExLlamaV2Cache, ExLlamaV2Cache_Q4, ExLlamaV2Cache_Q6, ExLlamaV2Cache_Q8  # noqa: F401
 

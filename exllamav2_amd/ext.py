@@ -1134,6 +1134,18 @@ class ExtC:
             self._ptr(workspace, torch.float32, "workspace"), self._ptr(history, torch.int32, "history"),
             self._ptr(hist_pos, torch.int32, "hist_pos"), history.shape[-1], int(pos_inc), self._stream(logits)))
 
+    def spec_accept_draft(self, cand, ids, history, pos, stats, K: int, ngram: int, forced=None, draft_only: bool = False) -> None:
+        """The tail of a speculative greedy step (include/exl2_hip.h exl2_spec_accept_draft): accept the drafts ids[1..K] that cand
+        confirms, log them in history, advance pos, count in stats, draft the next K tokens into ids[1..K].  int32 device tensors;
+        ngram = the longest context the drafter matches (max_ngram - 1); draft_only: drafts for the position as it stands."""
+        if ids.numel() != K + 1: raise RuntimeError("spec_accept_draft: ids must hold K + 1 tokens")
+        if not draft_only and (_is_none(cand) or cand.numel() != K + 1 or _is_none(stats) or stats.numel() < K + 3):
+            raise RuntimeError("spec_accept_draft: cand must hold K + 1 tokens and stats K + 3 counters")
+        self.lib.check(self.lib.exl2_spec_accept_draft(
+            self._ptr(cand, torch.int32, "cand"), self._ptr(ids, torch.int32, "ids"), self._ptr(history, torch.int32, "history"),
+            self._ptr(pos, torch.int32, "pos"), self._ptr(stats, torch.int32, "stats"), self._ptr(forced, torch.int32, "forced"),
+            0 if _is_none(forced) else forced.numel(), int(K), int(ngram), history.numel(), int(bool(draft_only)), self._stream(ids)))
+
     def add_i32_(self, t, value: int) -> None:
         self.lib.check(self.lib.exl2_add_i32(self._ptr(t, torch.int32, "t"), t.numel(), int(value), self._stream(t)))
 

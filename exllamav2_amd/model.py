@@ -335,6 +335,7 @@ class GreedyGraphDecoder:
         """loras: ExLlamaV2Lora adapters every step applies.  Such a decoder takes the module-by-module step (the chained decode
         kernels carry no adapters), still one captured graph per token."""
         self.model, self.cache, self.b = model, cache, batch_size
+        self.q_len = 1                # rows per sequence of a step (b = sequences x q_len; speculative.SpeculativeGraphDecoder: K + 1)
         self.loras = list(loras) if loras else None
         cfg, dev = model.config, model.device
         pages_per_seq = cache.max_seq_len // PAGE_SIZE
@@ -453,9 +454,11 @@ class GreedyGraphDecoder:
         m, ext, cfg, ch = self.model, self.model.ext, self.model.config, self.chain
         b, plan = self.b, ch["plan"]
         x2 = self.x.view(b, cfg.hidden_size)
-        q = m.temp_q[:b].view(b, 1, cfg.num_attention_heads, cfg.head_dim)
-        k = m.temp_k[:b].view(b, 1, cfg.num_key_value_heads, cfg.head_dim)
-        v = m.temp_v[:b].view(b, 1, cfg.num_key_value_heads, cfg.head_dim)
+        seqs, q_len = b // self.q_len, self.q_len
+        q = m.temp_q[:b].view(seqs, q_len, cfg.num_attention_heads, cfg.head_dim)
+        k = m.temp_k[:b].view(seqs, q_len, cfg.num_key_value_heads, cfg.head_dim)
+        v = m.temp_v[:b].view(seqs, q_len, cfg.num_key_value_heads, cfg.head_dim)
+        qr, kr, vr = q.view(b, -1), k.view(b, -1), v.view(b, -1)      # the same rows, one per index: what a row group slices
         xp_a, xp_b, ss_a, ss_b = ch["xp_a"], ch["xp_b"], ch["ss_a"], ch["ss_b"]
         overlap = "flags" in ch
         # Row groups: a launch of the lean kernel takes the rows whose staged copy fits in LDS (<= 16; <= 4 in its wave-private
@@ -511,10 +514,10 @@ class GreedyGraphDecoder:
                 skip_hn = attn.chain_skip_head_norm(self.cache)
                 for r0, r1 in groups_h:
                     ss, cnt = pa.inp(r0, r1, "q|k|v")
-                    ext.q_attn_forward_1_chain(attn.q_handle, xp_a[r0:r1], ss, cnt, r1 - r0, q[r0:r1], k[r0:r1], v[r0:r1], skip_head_norm=skip_hn)
+                    ext.q_attn_forward_1_chain(attn.q_handle, xp_a[r0:r1], ss, cnt, r1 - r0, qr[r0:r1], kr[r0:r1], vr[r0:r1], skip_head_norm=skip_hn)
                 # (self.block_table is the identity: the launch may address the rows directly)
                 ao = attn.attend_chain(q, k, v, self.cache, self.cache_seqlens, self.block_table, o_inv, head_norm_pending=skip_hn,
-                                       rope_now=ch.get("rope_now"), identity_table=True)
+                                       rope_now=ch.get("rope_now"), identity_table=True).view(b, -1)
                 # every producer of the residual stream publishes it times its consumer's norm weight, in that consumer's order
                 nxt, nxt_w = (plan[i + 1][0], plan[i + 1][3]) if i + 1 < len(plan) else (ch["head_inv"], ch["norm_head"])
                 if in_m == "moe":

@@ -534,6 +534,20 @@ int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int voca
                           const float* randoms, int n_randoms, const int* counter,
                           int* out_tokens, float* out_probs, float* workspace,
                           int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream);
+/* The tail of a speculative greedy decode step (csrc/spec_decode.hip), one launch of one workgroup behind exl2_argmax_rows.
+   cand [K + 1]: the arg-max of the verify step's rows; ids [K + 1]: the step's input token and its K drafts; history [hist_len]:
+   history[j] = the token at sequence index j, prompt included; pos [1]: the cache length p (history[p] == ids[0]); stats
+   [>= K + 3]: steps, accepted drafts, a histogram of the accepted count over 0 .. K.
+   Accept: n_acc = the number of leading i < K with ids[i + 1] == cand[i]; history[p + 1 .. p + 1 + n_acc] = cand[0 .. n_acc],
+   pos = p + n_acc + 1, ids[0] = cand[n_acc], stats[0] += 1, stats[1] += n_acc, stats[2 + n_acc] += 1.
+   Draft: with L = pos + 1 and seq = history[0 .. L), for n = min(ngram, L - 1) down to 1 the largest j in [n - 1, L - 2] with
+   seq[j - n + 1 .. j] == seq[L - n .. L - 1]; at the first n that has one, ids[1 + i] = ext[j + 1 + i] for i < K, ext = seq
+   extended by the drafts themselves; no match: every draft is seq[L - 1].  forced (nullable, [forced_len]): drafts are
+   forced[L + i] instead, seq[L - 1] beyond forced_len (tests, controlled acceptance).
+   draft_only != 0: no accept step -- cand and stats may be null, pos and ids[0] stay, the drafts are made for L = p + 1.
+   1 <= K <= 15, 1 <= ngram <= 7.  A position with p + K + 2 > hist_len (draft_only: p + 1 > hist_len) changes nothing. */
+int exl2_spec_accept_draft(const int* cand, int* ids, int* history, int* pos, int* stats, const int* forced, int forced_len,
+                           int K, int ngram, int hist_len, int draft_only, void* stream);
 int exl2_graph_begin_capture(void* stream);
 int exl2_graph_end_capture(void* stream, void** graph_exec);
 int exl2_graph_launch(void* graph_exec, void* stream);
