@@ -273,7 +273,21 @@ def apply_rep_penalty(sequence, penalty_max, sustain, decay, alpha_frequency, al
     `sustain + decay` tokens of each sequence backwards; the first encounter of a token divides (positive logit) or
     multiplies its logit by the repetition penalty and subtracts the presence penalty, every encounter subtracts the
     frequency penalty; inside the decay range the three penalties move linearly towards 1 / 0 / 0 (fp32 steps).
-    sequence int64 [bsz, seq_len], logits fp32 [bsz, 1, vocab] on the host, modified in place."""
+    sequence int64 [bsz, seq_len], logits fp32 [bsz, 1, vocab] on the host, modified in place -- what the reference passes.
+    Logits on the DEVICE (a caller of our own that keeps them there) take the kernel instead (csrc/penalties.hip): same bits."""
+    if logits.device.type == "cuda":
+        bsz, seq_len = sequence.shape[0], sequence.shape[-1]
+        if seq_len == 0:
+            return
+        if logits.dtype != _torch.float32 or not logits.is_contiguous():
+            raise RuntimeError("exllamav2_ext.apply_rep_penalty: device logits must be contiguous fp32")
+        lg = logits.view(bsz, -1)
+        seq = sequence.view(bsz, seq_len)
+        # (ids that do not fit an int32 lie outside every vocabulary: any such value does)
+        hist = _torch.where((seq >= 0) & (seq < 2 ** 31), seq, _torch.full_like(seq, -1)).to(lg.device, dtype=_torch.int32).contiguous()
+        pos = _torch.full((bsz,), seq_len - 1, dtype=_torch.int32, device=lg.device)
+        _e.apply_penalties(lg, lg, hist, pos, penalty_max, sustain, decay, alpha_frequency, alpha_presence)
+        return
     f32 = _np.float32
     seq = sequence.numpy()
     lg = logits.view(logits.shape[0], -1).numpy()
@@ -326,8 +340,9 @@ def sample_basic(logits, temperature, top_k, top_p, top_a, min_p, tfs, typical, 
                  post_temperature, xtc_mask, xtc_probability, xtc_threshold, min_temp, max_temp, temp_exponent,
                  smoothing_factor, skew):
     """ext_sampling.cpp:93-301.  Greedy (top_k == 1 or temperature ~ 0: what ExLlamaV2Sampler.Settings.greedy() asks for and
-    test_inference.py measures) is an arg-max under the logit filter.  Temperature / top-k (1..500) / top-p / min-p -- the
-    reference's default Settings (sampler.py:54-69) -- run on the DEVICE sampler (csrc/sampling.hip: same candidates, same
+    test_inference.py measures) is an arg-max under the logit filter.  Temperature / top-k (1..500) / top-p / min-p -- what the
+    reference's default Settings (sampler.py:54-69) leave for this call once apply_rep_penalty above has applied their
+    token_repetition_penalty of 1.025 on the host logits -- run on the DEVICE sampler (csrc/sampling.hip: same candidates, same
     order, same fp32 threshold sums, same random recurrence as the CPU sampler).  Everything else of the sampler chain
     (top-a, tfs, typical, mirostat, XTC, skew, smoothing, dynamic temperature, the top-token report with sampling, top_k = 0
     or > 500) is outside the quantized forward path and raises."""

@@ -44,6 +44,9 @@ PROTOTYPES = {
     "exl2_add_i32": (ci, [vp, ci, ci, vp]),
     "exl2_sample_rows": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, cf, vp, vp, vp, vp]),
     "exl2_sample_rows_step": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
+    "exl2_sample_rows_step2": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp]),
+    # sampler penalties + token bias (csrc/penalties.hip)
+    "exl2_apply_penalties": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, vp, cf, ci, ci, cf, cf, vp, vp, vp]),
     # quantized KV cache
     "exl2_fp16_to_q_kv": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
     "exl2_q_to_fp16_kv": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, ci, ci, vp]),
@@ -143,6 +146,7 @@ PROTOTYPES = {
     "exl2_prefill_route_info": (ci, [C.POINTER(ci)]),
     # speculative greedy decoding (csrc/spec_decode.hip)
     "exl2_spec_accept_draft": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    "exl2_spec_accept_draft2": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp]),
     # graphs
     "exl2_graph_begin_capture": (ci, [vp]),
     "exl2_graph_end_capture": (ci, [vp, C.POINTER(vp)]),

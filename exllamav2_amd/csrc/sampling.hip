@@ -45,6 +45,9 @@ struct SampleArgs
     const float* randoms; const int* counter; int n_randoms;
     int* history; int* hist_pos; int hist_stride, pos_inc;
     int quick;                        // REG: quick select in front of the radix passes (EXL2_SAMPLE_QUICK=0: A/B, tests)
+    // row r takes randoms[(*counter + r) % n_randoms] as its point, no recurrence: the rows are positions of ONE sequence, each
+    // sampled as the reference's speculative verification does, by a sample() call of batch 1 with a fresh random.random()
+    int per_row_random;
 };
 
 // Row walks.  A row whose length and stride are multiples of 4 elements on a 16-byte-aligned base (every real vocabulary) is
@@ -548,8 +551,9 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
         normalize(n);
     }
     if (!lead) return;
-    float random = a.randoms ? a.randoms[(unsigned)a.counter[0] % (unsigned)a.n_randoms] : a.random;
-    for (int r = 0; r < row; r++)                                   // ext_sampling.cpp:286-296, once per earlier row
+    const unsigned ctr = a.randoms ? (unsigned)a.counter[0] + (a.per_row_random ? (unsigned)row : 0u) : 0u;
+    float random = a.randoms ? a.randoms[ctr % (unsigned)a.n_randoms] : a.random;
+    for (int r = 0; r < (a.per_row_random ? 0 : row); r++)          // ext_sampling.cpp:286-296, once per earlier row
     {
         float x = random;
         for (int j = 0; j < 10; j++) { x = (float)((double)x + (1.337 + (double)random)); x *= x; x = fmodf(x, 1.0f); }
@@ -627,11 +631,12 @@ int exl2_sample_rows(const void* logits, int logits_f32, int rows, int vocab, in
 // replays from ONE graph), the token is written to out_tokens, logged at history[row, hist_pos[row] + pos_inc] and the position
 // is advanced -- exactly what exl2_argmax_rows does for greedy decoding.  *counter is NOT advanced here (every row reads it):
 // the graph appends exl2_add_i32(counter, 1, 1).  Values in randoms must lie in [0, 1) (host contract; not checked on the device).
-int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
-                          float temperature, int top_k, float top_p, float min_p,
-                          const float* randoms, int n_randoms, const int* counter,
-                          int* out_tokens, float* out_probs, float* workspace,
-                          int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream)
+// exl2_sample_rows_step2: the same with per_row_random -- row r's point is randoms[(*counter + r) % n_randoms], no recurrence.
+static int sample_step(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                       float temperature, int top_k, float top_p, float min_p,
+                       const float* randoms, int n_randoms, const int* counter, int per_row_random,
+                       int* out_tokens, float* out_probs, float* workspace,
+                       int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream)
 {
     EXL2_REQUIRE(randoms && counter && n_randoms >= 1, "sample_rows_step: random buffer / counter missing");
     EXL2_REQUIRE(!history || hist_pos, "sample_rows_step: history needs hist_pos");
@@ -640,9 +645,29 @@ int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int voca
     a.logits = logits; a.ld = ld; a.vocab = vocab; a.filter = (const u8*)logit_filter;
     a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.min_p = min_p;
     a.out_tokens = out_tokens; a.out_probs = out_probs; a.ws = workspace;
-    a.randoms = randoms; a.n_randoms = n_randoms; a.counter = counter;
+    a.randoms = randoms; a.n_randoms = n_randoms; a.counter = counter; a.per_row_random = per_row_random ? 1 : 0;
     a.history = history; a.hist_pos = hist_pos; a.hist_stride = hist_stride; a.pos_inc = pos_inc;
     return sample_launch(a, logits_f32, rows, 0.0f, stream);
+}
+
+int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                          float temperature, int top_k, float top_p, float min_p,
+                          const float* randoms, int n_randoms, const int* counter,
+                          int* out_tokens, float* out_probs, float* workspace,
+                          int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream)
+{
+    return sample_step(logits, logits_f32, rows, vocab, ld, logit_filter, temperature, top_k, top_p, min_p, randoms, n_randoms, counter, 0,
+                       out_tokens, out_probs, workspace, history, hist_pos, hist_stride, pos_inc, stream);
+}
+
+int exl2_sample_rows_step2(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                           float temperature, int top_k, float top_p, float min_p,
+                           const float* randoms, int n_randoms, const int* counter, int per_row_random,
+                           int* out_tokens, float* out_probs, float* workspace,
+                           int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream)
+{
+    return sample_step(logits, logits_f32, rows, vocab, ld, logit_filter, temperature, top_k, top_p, min_p, randoms, n_randoms, counter,
+                       per_row_random, out_tokens, out_probs, workspace, history, hist_pos, hist_stride, pos_inc, stream);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 struct SpecArgs
 {
     const int* cand; int* ids; int* history; int* pos; int* stats; const int* forced;
+    int* rand_counter;                          // nullable: advanced by the tokens the step emits (sampled verification)
     int forced_len, K, N, hist_len, draft_only;
 };
 
@@ -103,12 +104,14 @@ KERNEL void __launch_bounds__(1024) spec_accept_draft_kernel(const SpecArgs a)
     a.stats[0] += 1;
     a.stats[1] += n_acc;
     a.stats[2 + n_acc] += 1;
+    // one random point per emitted token, as unspeculated sampled decoding consumes them (the rows read counter + r)
+    if (a.rand_counter) a.rand_counter[0] += n_acc + 1;
 }
 
 extern "C" {
 
-int exl2_spec_accept_draft(const int* cand, int* ids, int* history, int* pos, int* stats, const int* forced, int forced_len,
-                           int K, int ngram, int hist_len, int draft_only, void* stream)
+int exl2_spec_accept_draft2(const int* cand, int* ids, int* history, int* pos, int* stats, const int* forced, int forced_len,
+                            int K, int ngram, int hist_len, int draft_only, int* rand_counter, void* stream)
 {
     EXL2_REQUIRE(ids && history && pos, "spec_accept_draft: null argument");
     EXL2_REQUIRE(draft_only || (cand && stats), "spec_accept_draft: the accept step needs cand and stats");
@@ -116,11 +119,17 @@ int exl2_spec_accept_draft(const int* cand, int* ids, int* history, int* pos, in
     EXL2_REQUIRE(ngram >= 1 && ngram <= SPEC_MAX_N, "spec_accept_draft: n-gram context %d must be in 1..%d", ngram, SPEC_MAX_N);
     EXL2_REQUIRE(hist_len >= K + 2, "spec_accept_draft: hist_len %d holds no step of %d rows", hist_len, K + 1);
     EXL2_REQUIRE(!forced || forced_len >= 0, "spec_accept_draft: forced_len %d", forced_len);
-    const SpecArgs a{cand, ids, history, pos, stats, forced, forced ? forced_len : 0, K, ngram, hist_len, draft_only ? 1 : 0};
+    const SpecArgs a{cand, ids, history, pos, stats, forced, rand_counter, forced ? forced_len : 0, K, ngram, hist_len, draft_only ? 1 : 0};
     // every thread takes one j per stride: a short log does not need sixteen waves to meet at the barriers
     LAUNCH(spec_accept_draft_kernel, dim3(1), dim3(hist_len <= 4096 ? 256 : 1024), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return EXL2_OK;
+}
+
+int exl2_spec_accept_draft(const int* cand, int* ids, int* history, int* pos, int* stats, const int* forced, int forced_len,
+                           int K, int ngram, int hist_len, int draft_only, void* stream)
+{
+    return exl2_spec_accept_draft2(cand, ids, history, pos, stats, forced, forced_len, K, ngram, hist_len, draft_only, nullptr, stream);
 }
 
 }  // extern "C"

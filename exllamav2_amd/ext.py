@@ -1117,34 +1117,96 @@ class ExtC:
         return workspace
 
     def sample_rows_step(self, logits, temperature: float, top_k: int, top_p: float, min_p: float, randoms, counter,
-                         out_tokens, out_probs, workspace, history, hist_pos, pos_inc: int = 1, vocab: int | None = None) -> None:
+                         out_tokens, out_probs, workspace, history, hist_pos, pos_inc: int = 1, vocab: int | None = None,
+                         per_row_random: bool = False) -> None:
         """sample_rows as the last launch of a decode-step graph (include/exl2_hip.h exl2_sample_rows_step): the random point is
         randoms[counter[0] % len(randoms)] (fp32 / int32 device tensors), the token is logged and the position advanced like
-        argmax_rows does.  The caller appends add_i32_(counter, 1)."""
+        argmax_rows does.  The caller appends add_i32_(counter, 1).  per_row_random (exl2_sample_rows_step2): row r takes
+        randoms[(counter[0] + r) % len(randoms)] and there is no recurrence; history / hist_pos may then be None (nothing logged)."""
         ld = logits.shape[-1]
         rows = logits.numel() // ld
         v = int(vocab or ld)
         if workspace.numel() < rows * v:
             raise RuntimeError("sample_rows_step: workspace smaller than rows x vocab")
-        self.lib.check(self.lib.exl2_sample_rows_step(
-            self._ptr(logits, None, "logits"), int(logits.dtype == torch.float32), rows, v, ld, None,
-            float(temperature), int(top_k), float(top_p), float(min_p),
-            self._ptr(randoms, torch.float32, "randoms"), randoms.numel(), self._ptr(counter, torch.int32, "counter"),
-            self._ptr(out_tokens, torch.int32, "out_tokens"), self._ptr(out_probs, torch.float32, "out_probs"),
-            self._ptr(workspace, torch.float32, "workspace"), self._ptr(history, torch.int32, "history"),
-            self._ptr(hist_pos, torch.int32, "hist_pos"), history.shape[-1], int(pos_inc), self._stream(logits)))
+        args = (self._ptr(logits, None, "logits"), int(logits.dtype == torch.float32), rows, v, ld, None,
+                float(temperature), int(top_k), float(top_p), float(min_p),
+                self._ptr(randoms, torch.float32, "randoms"), randoms.numel(), self._ptr(counter, torch.int32, "counter"))
+        tail = (self._ptr(out_tokens, torch.int32, "out_tokens"), self._ptr(out_probs, torch.float32, "out_probs"),
+                self._ptr(workspace, torch.float32, "workspace"), self._ptr(history, torch.int32, "history"),
+                self._ptr(hist_pos, torch.int32, "hist_pos"), 0 if _is_none(history) else history.shape[-1], int(pos_inc),
+                self._stream(logits))
+        if per_row_random:
+            self.lib.check(self.lib.exl2_sample_rows_step2(*args, 1, *tail))
+        else:
+            self.lib.check(self.lib.exl2_sample_rows_step(*args, *tail))
 
-    def spec_accept_draft(self, cand, ids, history, pos, stats, K: int, ngram: int, forced=None, draft_only: bool = False) -> None:
+    @staticmethod
+    def penalty_ramps(penalty: float, decay: int, alpha_frequency: float, alpha_presence: float):
+        """The values of the three penalties inside the decay range, as apply_rep_penalty_cpu reaches them (cpp/sampling.cpp:54-62,
+        100-105): fp32 [3, decay], row c column k = start after k sequential fp32 additions of (target - start) / decay; None
+        when decay == 0.  They depend on the settings only, so the device kernel is left nothing serial."""
+        import numpy as np
+        decay = int(decay)
+        if decay <= 0:
+            return None
+        f32 = np.float32
+        rows = []
+        for start, target in ((penalty, 1.0), (alpha_frequency, 0.0), (alpha_presence, 0.0)):
+            d = (f32(target) - f32(start)) / f32(decay)
+            rows.append(np.add.accumulate(np.concatenate([np.array([start], dtype=f32), np.full(decay - 1, d, dtype=f32)]), dtype=f32))
+        return torch.from_numpy(np.stack(rows))
+
+    def apply_penalties(self, logits, out, history, hist_pos, penalty: float = 1.0, sustain: int = -1, decay: int = 0,
+                        alpha_frequency: float = 0.0, alpha_presence: float = 0.0, ramps=None, token_bias=None,
+                        vocab: int | None = None, rows_share_sequence: bool = False, tail=None, pos_offset: int = 0) -> None:
+        """The reference sampler's penalties and token bias on the device (include/exl2_hip.h exl2_apply_penalties; the reference:
+        apply_rep_penalty, then logits += token_bias -- sampler.py:408-429).  logits fp16 / fp32 [rows, ld]; out fp32 [rows, vocab];
+        history int32 [rows, stride] (or one row with rows_share_sequence), hist_pos int32: row r's sequence is
+        history[r, : hist_pos[r] + pos_offset + 1], read on the device.  ramps: penalty_ramps(...) on the device, made here when
+        None and decay > 0 (a caller inside a captured graph passes its own)."""
+        ld = logits.shape[-1]
+        rows = logits.numel() // ld
+        v = int(vocab or ld)
+        if logits.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError(f"apply_penalties: logits must be fp16 or fp32, got {logits.dtype}")
+        if _is_none(out) or _is_none(history) or _is_none(hist_pos):
+            raise RuntimeError("apply_penalties: out, history and hist_pos are needed")
+        if out.numel() < rows * v:
+            raise RuntimeError("apply_penalties: out smaller than rows x vocab")
+        seqs = 1 if rows_share_sequence else rows
+        if history.numel() < seqs * history.shape[-1] or hist_pos.numel() < seqs:
+            raise RuntimeError("apply_penalties: history / hist_pos hold fewer sequences than there are rows")
+        if rows_share_sequence and rows > 1 and (_is_none(tail) or tail.numel() < rows - 1):
+            raise RuntimeError("apply_penalties: rows that share a sequence need a tail of rows - 1 tokens")
+        if not _is_none(token_bias) and token_bias.numel() < v:
+            raise RuntimeError("apply_penalties: token_bias must hold vocab entries")
+        if int(decay) > 0 and _is_none(ramps):
+            ramps = self.penalty_ramps(penalty, decay, alpha_frequency, alpha_presence).to(logits.device)
+        if not _is_none(ramps) and ramps.numel() < 3 * max(int(decay), 0):
+            raise RuntimeError("apply_penalties: ramps must be [3, decay]")
+        self.lib.check(self.lib.exl2_apply_penalties(
+            self._ptr(logits, None, "logits"), int(logits.dtype == torch.float32), rows, v, ld, self._ptr(out, torch.float32, "out"),
+            self._ptr(history, torch.int32, "history"), history.shape[-1], self._ptr(hist_pos, torch.int32, "hist_pos"),
+            int(pos_offset), int(bool(rows_share_sequence)), self._ptr(tail, torch.int32, "tail"),
+            float(penalty), int(sustain), int(decay), float(alpha_frequency), float(alpha_presence),
+            self._ptr(ramps, torch.float32, "ramps"), self._ptr(token_bias, torch.float32, "token_bias"), self._stream(logits)))
+
+    def spec_accept_draft(self, cand, ids, history, pos, stats, K: int, ngram: int, forced=None, draft_only: bool = False,
+                          rand_counter=None) -> None:
         """The tail of a speculative greedy step (include/exl2_hip.h exl2_spec_accept_draft): accept the drafts ids[1..K] that cand
         confirms, log them in history, advance pos, count in stats, draft the next K tokens into ids[1..K].  int32 device tensors;
-        ngram = the longest context the drafter matches (max_ngram - 1); draft_only: drafts for the position as it stands."""
+        ngram = the longest context the drafter matches (max_ngram - 1); draft_only: drafts for the position as it stands.
+        rand_counter (exl2_spec_accept_draft2, sampled verification): int32 [1], advanced by the number of tokens emitted."""
         if ids.numel() != K + 1: raise RuntimeError("spec_accept_draft: ids must hold K + 1 tokens")
         if not draft_only and (_is_none(cand) or cand.numel() != K + 1 or _is_none(stats) or stats.numel() < K + 3):
             raise RuntimeError("spec_accept_draft: cand must hold K + 1 tokens and stats K + 3 counters")
-        self.lib.check(self.lib.exl2_spec_accept_draft(
-            self._ptr(cand, torch.int32, "cand"), self._ptr(ids, torch.int32, "ids"), self._ptr(history, torch.int32, "history"),
-            self._ptr(pos, torch.int32, "pos"), self._ptr(stats, torch.int32, "stats"), self._ptr(forced, torch.int32, "forced"),
-            0 if _is_none(forced) else forced.numel(), int(K), int(ngram), history.numel(), int(bool(draft_only)), self._stream(ids)))
+        args = (self._ptr(cand, torch.int32, "cand"), self._ptr(ids, torch.int32, "ids"), self._ptr(history, torch.int32, "history"),
+                self._ptr(pos, torch.int32, "pos"), self._ptr(stats, torch.int32, "stats"), self._ptr(forced, torch.int32, "forced"),
+                0 if _is_none(forced) else forced.numel(), int(K), int(ngram), history.numel(), int(bool(draft_only)))
+        if _is_none(rand_counter):
+            self.lib.check(self.lib.exl2_spec_accept_draft(*args, self._stream(ids)))
+        else:
+            self.lib.check(self.lib.exl2_spec_accept_draft2(*args, self._ptr(rand_counter, torch.int32, "rand_counter"), self._stream(ids)))
 
     def add_i32_(self, t, value: int) -> None:
         self.lib.check(self.lib.exl2_add_i32(self._ptr(t, torch.int32, "t"), t.numel(), int(value), self._stream(t)))

@@ -571,9 +571,66 @@ class GreedyGraphDecoder:
         if sm is None:
             ext.argmax_rows(self.logits, self.ids, cfg.vocab_size, self.history, self.cache_seqlens, pos_inc=1)
             return
-        ext.sample_rows_step(self.logits, sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"], sm["randoms"], sm["counter"],
+        logits = self._penalised_logits(sm)
+        ext.sample_rows_step(logits, sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"], sm["randoms"], sm["counter"],
                              self.ids, sm["probs"], sm["ws"], self.history, self.cache_seqlens, pos_inc=1, vocab=cfg.vocab_size)
         ext.add_i32_(sm["counter"], 1)
+
+    # ---- the reference sampler's penalties and token bias (sampler.py:408-429), on the device: csrc/penalties.hip --------------
+    PENALTY_DEFAULTS = {"token_repetition_penalty": 1.0, "token_repetition_range": -1, "token_repetition_decay": 0,
+                        "token_frequency_penalty": 0.0, "token_presence_penalty": 0.0, "token_bias": None}
+
+    def _penalty_state(self, kw: dict, old=None):
+        """The penalty / bias settings of a sampled run (the reference Settings' names) as what the launches need: None when all of
+        them are neutral -- the sampled step is then exactly the launches without them.  `old`: a state whose buffers are reused
+        when its settings are these."""
+        unknown = set(kw) - set(self.PENALTY_DEFAULTS)
+        if unknown:
+            raise TypeError(f"sampled decoding: unknown setting(s) {sorted(unknown)}")
+        st = self.PENALTY_DEFAULTS | kw
+        bias = st["token_bias"]
+        key = (float(st["token_repetition_penalty"]), int(st["token_repetition_range"]), int(st["token_repetition_decay"]),
+               float(st["token_frequency_penalty"]), float(st["token_presence_penalty"]))
+        if key[0] == 1.0 and key[3] == 0.0 and key[4] == 0.0 and bias is None:
+            return None
+        if key[1] < -1 or key[2] < 0:
+            raise RuntimeError(f"sampled decoding: token_repetition_range {key[1]} / token_repetition_decay {key[2]}")
+        cfg, dev = self.model.config, self.logits.device
+        if bias is not None:
+            bias = bias.detach().reshape(-1).to(torch.float32).cpu()
+            if bias.numel() < cfg.vocab_size:
+                raise RuntimeError("sampled decoding: token_bias must hold one entry per token of the vocabulary")
+            bias = bias[:cfg.vocab_size].contiguous()
+        if old is not None and old["key"] == key and (bias is None) == (old["bias"] is None) and (
+                bias is None or torch.equal(bias, old["bias_host"])):
+            return old
+        ramps = self.model.ext.penalty_ramps(key[0], key[2], key[3], key[4])
+        return {"key": key, "bias_host": bias, "bias": None if bias is None else bias.to(dev),
+                "ramps": None if ramps is None else ramps.to(dev),
+                "out": torch.zeros((self.b, cfg.vocab_size), dtype=torch.float32, device=dev)}
+
+    def _penalised_logits(self, sm, pos_offset: int = 0):
+        """penalties, then bias (the reference's order), from the step's fp16 logits into the sampled state's fp32 buffer; the logits
+        themselves when the settings are neutral"""
+        pen = sm.get("pen")
+        if pen is None:
+            return self.logits
+        k = pen["key"]
+        self.model.ext.apply_penalties(self.logits, pen["out"], self.history, self.cache_seqlens, k[0], k[1], k[2], k[3], k[4],
+                                       ramps=pen["ramps"], token_bias=pen["bias"], vocab=self.model.config.vocab_size,
+                                       pos_offset=pos_offset)
+        return pen["out"]
+
+    def _check_window_known(self, pen):
+        """the penalties look at history[:, beg .. pos]: a window that starts below what reset() was told is refused"""
+        if pen is None:
+            return
+        _, sustain, decay = pen["key"][:3]
+        seq_len = self.pos + 1
+        beg = max(seq_len - (seq_len if sustain == -1 else sustain) - decay, 0)
+        if beg < getattr(self, "_known_from", 0) and seq_len - beg > 0:
+            raise RuntimeError(f"sampled decoding: the penalties look back to sequence index {beg}, but the token log is known from "
+                               f"{self._known_from} on only -- pass prompt_ids to reset()")
 
     def _overlapped(self) -> bool:
         return self.chain is not None and "flags" in self.chain and self.chain.get("stream_b") is not None
@@ -748,11 +805,26 @@ class GreedyGraphDecoder:
             self.stream.synchronize()
         return self
 
-    def reset(self, first_ids: torch.Tensor, seq_len: int = 0):
+    def reset(self, first_ids: torch.Tensor, seq_len: int = 0, prompt_ids=None):
+        """prompt_ids (int [b, seq_len + 1], last column = first_ids): the sequences so far, logged in history[:, :seq_len + 1] for
+        the sampler's penalties; without it only history[:, seq_len] = first_ids is known."""
+        seq_len = int(seq_len)
+        first = first_ids.to(torch.int32).view(-1)
+        if prompt_ids is not None:
+            prompt = prompt_ids.to(torch.int32).view(self.b, -1)
+            if prompt.shape[1] != seq_len + 1:
+                raise RuntimeError(f"decode: prompt_ids holds {prompt.shape[1]} tokens per sequence, seq_len + 1 = {seq_len + 1} are expected")
+            if not torch.equal(prompt[:, -1].cpu(), first.cpu()):
+                raise RuntimeError("decode: the last column of prompt_ids must be first_ids")
         with self._on_stream():
-            self.ids.copy_(first_ids.to(torch.int32).view(-1))
+            self.ids.copy_(first)
             self.cache_seqlens.fill_(seq_len)
-        self.pos = int(seq_len)
+            if prompt_ids is not None:
+                self.history[:, :seq_len + 1].copy_(prompt)
+            elif 0 <= seq_len < self.history.shape[1]:
+                self.history[:, seq_len].copy_(first)
+        self._known_from = 0 if prompt_ids is not None else seq_len
+        self.pos = seq_len
 
     def run(self, n_tokens: int, use_graph: bool = True):
         ext = self.model.ext
@@ -773,10 +845,14 @@ class GreedyGraphDecoder:
             if two:
                 self.stream.wait_event(self.chain["ev_b"])
 
-    def capture_sampled(self, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0, n_randoms: int = 4096):
+    def capture_sampled(self, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0, n_randoms: int = 4096,
+                        **penalties):
         """A second step graph whose last launches are the device sampler (exl2_sample_rows_step) + its counter increment instead
         of the arg-max: `run_sampled` with these settings then replays ONE graph per token -- the random points are read from a
-        device buffer the host fills before the run (n_randoms tokens ahead at most per fill)."""
+        device buffer the host fills before the run (n_randoms tokens ahead at most per fill).
+        penalties: token_repetition_penalty / _range / _decay, token_frequency_penalty, token_presence_penalty, token_bias (fp32
+        [vocab]) -- the reference Settings' names and meaning (sampler.py:54-69, 408-429).  Any of them off its neutral value puts
+        exl2_apply_penalties in front of the sampler, inside the same graph."""
         ext, cfg = self.model.ext, self.model.config
         if self._overlapped():
             raise RuntimeError("capture_sampled: not available on the experimental overlapped chain")
@@ -786,6 +862,7 @@ class GreedyGraphDecoder:
               "counter": torch.zeros((1,), dtype=torch.int32, device=dev),
               "probs": torch.zeros((self.b,), dtype=torch.float32, device=dev),
               "ws": torch.empty((self.b, cfg.vocab_size), dtype=torch.float32, device=dev)}
+        sm["pen"] = self._penalty_state(penalties)
         sm["graph"] = None
         if dev.type == "cuda":
             greedy_graph, self.graph = self.graph, None
@@ -804,13 +881,14 @@ class GreedyGraphDecoder:
         return self
 
     def run_sampled(self, n_tokens: int, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0,
-                    randoms=None, seed: int = 0, use_graph: bool = True):
+                    randoms=None, seed: int = 0, use_graph: bool = True, **penalties):
         """Decode `n_tokens` tokens per sequence with the DEVICE sampler (csrc/sampling.hip; the reference's sample_basic for
         these settings: ext_sampling.cpp:93-301) instead of the arg-max: per token the step's graph, then one
         `sample_rows` launch on the step's logits that overwrites the token fed to the next step, then the token log.
         The only thing the host supplies per token is the random point (`randoms[i]`, or `random.Random(seed)` like the
         reference's `random.random()` per sampling call, sampler.py:351) -- as a launch argument; nothing is read back, so
-        the loop stays asynchronous like run().  Rows of a batch share the point through the reference's recurrence."""
+        the loop stays asynchronous like run().  Rows of a batch share the point through the reference's recurrence.
+        penalties: as capture_sampled; applied on the device ahead of the sampler on either route."""
         import random as _random
         ext, cfg = self.model.ext, self.model.config
         if self._overlapped():
@@ -823,7 +901,9 @@ class GreedyGraphDecoder:
         if len(randoms) < n_tokens:
             raise RuntimeError("run_sampled: one random point per token is needed")
         sm = getattr(self, "_sampled", None)
-        if (sm is not None and n_tokens <= sm["randoms"].numel()
+        pen = self._penalty_state(penalties, old=(sm or {}).get("pen") or getattr(self, "_sample_pen", None))
+        self._check_window_known(pen)
+        if (sm is not None and n_tokens <= sm["randoms"].numel() and pen is sm.get("pen")
                 and (sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"]) == (float(temperature), int(top_k), float(top_p), float(min_p))):
             # settings of capture_sampled: the sampler is part of the step; the random points travel as ONE copy before the run,
             # then one graph launch per token (eager steps of the same launches where there is no graph)
@@ -848,6 +928,7 @@ class GreedyGraphDecoder:
             dev = self.logits.device
             self._sample_ws = torch.empty((self.b, cfg.vocab_size), dtype=torch.float32, device=dev)
             self._sample_probs = torch.zeros((self.b,), dtype=torch.float32, device=dev)
+        self._sample_pen = pen
         p0 = self.pos
         self.pos += n_tokens
         with self._on_stream():
@@ -858,7 +939,9 @@ class GreedyGraphDecoder:
                 else:
                     self.step_eager()
                 # the step's own arg-max has written its token to ids / history[:, p0 + i + 1]; the sampled one replaces both
-                ext.sample_rows(self.logits, temperature, top_k, top_p, min_p, float(randoms[i]), self.ids, self._sample_probs,
+                # (the position is one ahead already: the penalties' sequence ends at the step's input token)
+                logits = self.logits if pen is None else self._penalised_logits({"pen": pen}, pos_offset=-1)
+                ext.sample_rows(logits, temperature, top_k, top_p, min_p, float(randoms[i]), self.ids, self._sample_probs,
                                 workspace=self._sample_ws, vocab=cfg.vocab_size)
                 self.history[:, p0 + i + 1].copy_(self.ids)
 

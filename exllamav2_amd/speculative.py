@@ -1,10 +1,13 @@
-"""Speculative greedy decoding of one sequence: K drafted tokens are verified by one forward over K + 1 rows, the longest prefix the
-model's own arg-max confirms is kept -- and the whole verify step (embedding -> layers -> head -> arg-max -> accept -> next drafts)
-stays one captured graph with no host round trip, like model.GreedyGraphDecoder's.
+"""Speculative decoding of one sequence: K drafted tokens are verified by one forward over K + 1 rows, the longest prefix the
+model's own choice confirms is kept -- and the whole verify step (embedding -> layers -> head -> arg-max or sampler -> accept -> next
+drafts) stays one captured graph with no host round trip, like model.GreedyGraphDecoder's.
 
 Procedure = the reference's ExLlamaV2DynamicGenerator(use_ngram_draft=True) (exllamav2/generator/dynamic.py:1009-1058 drafting,
-:1139- verification) for greedy sampling; the drafter is a rule of our own on the device (csrc/spec_decode.hip: latest longest
-n-gram match, overlapping copy).  Greedy verification makes the emitted tokens independent of the drafts."""
+:1139- verification); the drafter is a rule of our own on the device (csrc/spec_decode.hip: latest longest n-gram match, overlapping
+copy).  Greedy verification makes the emitted tokens independent of the drafts.  Sampled verification (capture_sampled / run_sampled)
+samples every row with a random point of its own, after the reference's penalties over the row's own sequence -- the log plus the
+drafts that must have been accepted for the row to count -- and accepts a draft when the sampled token equals it; a random point is
+consumed per EMITTED token, so the tokens are those of unspeculated sampled decoding with the same points."""
 from __future__ import annotations
 
 import os
@@ -80,8 +83,27 @@ class SpeculativeGraphDecoder(GreedyGraphDecoder):
     # step first rewrites p' .. p' + K, which covers p' .. p + K because p' + K >= p + K.  So no row is ever rolled back.
     def _select_token(self):
         ext, cfg = self.model.ext, self.model.config
-        ext.argmax_rows(self.logits, self.cand, cfg.vocab_size)
-        ext.spec_accept_draft(self.cand, self.ids, self.history, self.cache_seqlens, self.stats_buf, self.K, self.N, forced=self.forced)
+        sm = getattr(self, "_sampling", None)
+        if sm is None:
+            ext.argmax_rows(self.logits, self.cand, cfg.vocab_size)
+            ext.spec_accept_draft(self.cand, self.ids, self.history, self.cache_seqlens, self.stats_buf, self.K, self.N, forced=self.forced)
+            return
+        # sampled verification: penalties over each row's own sequence, one random point per row, the counter moves with the tokens kept
+        logits = self._penalised_logits(sm)
+        ext.sample_rows_step(logits, sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"], sm["randoms"], sm["counter"],
+                             self.cand, sm["probs"], sm["ws"], None, None, pos_inc=0, vocab=cfg.vocab_size, per_row_random=True)
+        ext.spec_accept_draft(self.cand, self.ids, self.history, self.cache_seqlens, self.stats_buf, self.K, self.N, forced=self.forced,
+                              rand_counter=sm["counter"])
+
+    def _penalised_logits(self, sm, pos_offset: int = 0):
+        pen = sm.get("pen")
+        if pen is None:
+            return self.logits
+        k = pen["key"]
+        self.model.ext.apply_penalties(self.logits, pen["out"], self.history, self.cache_seqlens, k[0], k[1], k[2], k[3], k[4],
+                                       ramps=pen["ramps"], token_bias=pen["bias"], vocab=self.model.config.vocab_size,
+                                       rows_share_sequence=True, tail=self.ids[1:], pos_offset=pos_offset)
+        return pen["out"]
 
     def capture(self):
         """Warm-up + capture run two throw-away steps pointed at the LAST K + 1 cache slots; their K/V rows on all layers, ids,
@@ -178,8 +200,47 @@ class SpeculativeGraphDecoder(GreedyGraphDecoder):
         return {"steps": steps, "accepted": accepted, "hist": st[2:2 + self.s], "emitted": steps + accepted,
                 "tokens_per_step": (steps + accepted) / steps if steps else 0.0}
 
-    def capture_sampled(self, *a, **kw):
-        raise RuntimeError("sampling with speculation is not built")
+    # capture_sampled: GreedyGraphDecoder's -- capture() above with the sampled tail as the step's last launches
 
-    def run_sampled(self, *a, **kw):
-        raise RuntimeError("sampling with speculation is not built")
+    def run_sampled(self, n_steps: int, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0,
+                    randoms=None, seed: int = 0, use_graph: bool = True, **penalties):
+        """n_steps sampled verify steps with the settings of capture_sampled, asynchronously like run().  The random points
+        (`randoms`, or random.Random(seed)) are copied to the device once, for the most the run can consume -- n_steps x (K + 1),
+        which the buffer of capture_sampled must hold; the counter restarts at 0 and ends at the number of tokens emitted."""
+        import random as _random
+        ext = self.model.ext
+        sm = getattr(self, "_sampled", None)
+        if sm is None:
+            raise RuntimeError("run_sampled: sampling with speculation runs the step capture_sampled made -- call capture_sampled first")
+        pen = self._penalty_state(penalties, old=sm.get("pen"))
+        if pen is not sm.get("pen") or (sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"]) != (
+                float(temperature), int(top_k), float(top_p), float(min_p)):
+            raise RuntimeError("run_sampled: the settings differ from those of capture_sampled")
+        need = int(n_steps) * self.s
+        if need > sm["randoms"].numel():
+            raise RuntimeError(f"run_sampled: {n_steps} steps may consume {need} random points, the buffer holds {sm['randoms'].numel()} "
+                               f"(capture_sampled n_randoms)")
+        if self.pos + need > self.limit:
+            raise RuntimeError(f"decode: {self.pos} cached + {n_steps} steps of up to {self.s} new tokens exceed the cache / "
+                               f"max_seq_len ({self.limit} + {self.K} draft rows)")
+        if randoms is None:
+            rng = _random.Random(seed)
+            randoms = [rng.random() for _ in range(need)]
+        if len(randoms) < need:
+            raise RuntimeError(f"run_sampled: {need} random points are needed (one per row of every step)")
+        pts = torch.tensor([float(r) for r in randoms[:need]], dtype=torch.float32)
+        self.pos += need
+        with self._on_stream():
+            sptr = self.stream.cuda_stream if self.stream is not None else None
+            sm["randoms"][:need].copy_(pts, non_blocking=False)
+            sm["counter"].zero_()
+            if use_graph and sm.get("graph") is not None:
+                for _ in range(n_steps):
+                    ext.graph_launch(sm["graph"], sptr)
+            else:
+                self._sampling = sm
+                try:
+                    for _ in range(n_steps):
+                        self.step_eager()
+                finally:
+                    self._sampling = None

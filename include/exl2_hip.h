@@ -534,6 +534,26 @@ int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int voca
                           const float* randoms, int n_randoms, const int* counter,
                           int* out_tokens, float* out_probs, float* workspace,
                           int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream);
+/* The same with per_row_random: != 0 gives row r the point randoms[(*counter + r) % n_randoms] and no recurrence -- the rows are
+   the positions of one sequence, each sampled like a sample() call of batch 1 with a fresh random.random() (the reference's
+   speculative verification, dynamic.py).  per_row_random = 0 is exl2_sample_rows_step. */
+int exl2_sample_rows_step2(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                           float temperature, int top_k, float top_p, float min_p,
+                           const float* randoms, int n_randoms, const int* counter, int per_row_random,
+                           int* out_tokens, float* out_probs, float* workspace,
+                           int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream);
+/* Repetition / frequency / presence penalties and the token bias of the reference's sampler on the device (csrc/penalties.hip):
+   out[row, :] = apply_rep_penalty_cpu (cpp/sampling.cpp:20-110) of float(logits[row, :vocab]), then + token_bias in fp32
+   (sampler.py:408-429), bit for bit.  logits [rows, ld] fp16 or fp32 (logits_f32), out fp32 [rows, vocab] (may be the fp32 logits
+   themselves when ld == vocab).  Row r's sequence is history[r, 0 .. hist_pos[r] + pos_offset] (int32 [*, hist_stride], read on
+   the device at launch); rows_share_sequence != 0: every row takes history row 0 / hist_pos[0], row r followed by tail[0 .. r - 1].
+   sustain = -1: the whole sequence.  ramps (required when decay > 0): device fp32 [3, decay] made by the host, ramps[c][k] = penalty
+   (c = 0) / alpha_frequency (1) / alpha_presence (2) after k sequential fp32 additions of (target - start) / decay, target 1 / 0 /
+   0.  token_bias: nullable fp32 [vocab].  Ids outside [0, vocab) change nothing.  No window length is refused. */
+int exl2_apply_penalties(const void* logits, int logits_f32, int rows, int vocab, int ld, float* out,
+                         const int* history, int hist_stride, const int* hist_pos, int pos_offset, int rows_share_sequence,
+                         const int* tail, float penalty, int sustain, int decay, float alpha_frequency, float alpha_presence,
+                         const float* ramps, const float* token_bias, void* stream);
 /* The tail of a speculative greedy decode step (csrc/spec_decode.hip), one launch of one workgroup behind exl2_argmax_rows.
    cand [K + 1]: the arg-max of the verify step's rows; ids [K + 1]: the step's input token and its K drafts; history [hist_len]:
    history[j] = the token at sequence index j, prompt included; pos [1]: the cache length p (history[p] == ids[0]); stats
@@ -548,6 +568,10 @@ int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int voca
    1 <= K <= 15, 1 <= ngram <= 7.  A position with p + K + 2 > hist_len (draft_only: p + 1 > hist_len) changes nothing. */
 int exl2_spec_accept_draft(const int* cand, int* ids, int* history, int* pos, int* stats, const int* forced, int forced_len,
                            int K, int ngram, int hist_len, int draft_only, void* stream);
+/* The same behind a sampler (cand = the rows' sampled tokens): rand_counter (nullable, int32 [1]) is advanced by n_acc + 1, the
+   random points the emitted tokens consumed; untouched with draft_only. */
+int exl2_spec_accept_draft2(const int* cand, int* ids, int* history, int* pos, int* stats, const int* forced, int forced_len,
+                            int K, int ngram, int hist_len, int draft_only, int* rand_counter, void* stream);
 int exl2_graph_begin_capture(void* stream);
 int exl2_graph_end_capture(void* stream, void** graph_exec);
 int exl2_graph_launch(void* graph_exec, void* stream);
