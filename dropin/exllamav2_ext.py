@@ -343,31 +343,63 @@ def sample_basic(logits, temperature, top_k, top_p, top_a, min_p, tfs, typical, 
     test_inference.py measures) is an arg-max under the logit filter.  Temperature / top-k (1..500) / top-p / min-p -- what the
     reference's default Settings (sampler.py:54-69) leave for this call once apply_rep_penalty above has applied their
     token_repetition_penalty of 1.025 on the host logits -- run on the DEVICE sampler (csrc/sampling.hip: same candidates, same
-    order, same fp32 threshold sums, same random recurrence as the CPU sampler).  Everything else of the sampler chain
-    (top-a, tfs, typical, mirostat, XTC, skew, smoothing, dynamic temperature, the top-token report with sampling, top_k = 0
-    or > 500) is outside the quantized forward path and raises."""
+    order, same fp32 threshold sums, same random recurrence as the CPU sampler), and so does the rest of the chain: top-a,
+    typical, mirostat (the updated mu list is returned: the reference does `settings.mirostat_mu = m`), post-softmax / dynamic
+    temperature, smoothing, skew and the top-token report (exl2_sample_rows_chain).  Refused: XTC (xtc_cpu reads one entry past the
+    candidates and compares an index with a probability: its result depends on stale buffer contents, nothing defined to match),
+    typical together with return_top_tokens (the pick then depends on the reference's partially sorted buffer), top_k = 0 or
+    > 500 (the reference's quicksort regime has no defined tie order), and -- for now -- tfs: the device sampler serves it
+    (ExtC.sample_rows_chain, the decoders), but tests/test_sampling.py pins this binding's refusal of it, so it stays refused here
+    until that test is changed."""
     greedy = top_k == 1 or temperature < 0.01
     has_filter = logit_filter is not None and logit_filter.device.type != "meta"
     if not greedy:
-        unsupported = [n for n, on in (("top_a", top_a > 0.0), ("tfs", 0.0 < tfs < 1.0), ("typical", 0.0 < typical < 1.0),
-                                       ("mirostat", bool(mirostat)), ("xtc", bool(xtc_probability and xtc_probability > 0.0)),
-                                       ("post_temperature / dynamic temperature", post_temperature != 1.0 or max_temp > min_temp),
-                                       ("smoothing_factor", smoothing_factor > 0.0), ("skew", skew != 0.0),
-                                       ("return_top_tokens", output_ktokens is not None and output_ktokens.device.type != "meta"),
+        has_k = output_ktokens is not None and output_ktokens.device.type != "meta"
+        unsupported = [n for n, on in (("XTC (xtc_cpu reads stale buffer contents: no defined behaviour to match)",
+                                        bool(xtc_probability and xtc_probability > 0.0)),
+                                       ("tfs (served by the device sampler, still refused by this binding: see the docstring)",
+                                        0.0 < tfs < 1.0),
+                                       ("typical with return_top_tokens (the pick depends on the reference's partial sort)",
+                                        0.0 < typical < 1.0 and has_k),
                                        ("top_k outside 1..500", not (1 <= top_k <= 500 and top_k < logits.shape[-1])))
                        if on]
         if unsupported:
             raise NotImplementedError("exllamav2_ext.sample_basic: " + ", ".join(unsupported) + " not built in this drop-in "
-                                      "(device sampler: temperature, top_k 1..500, top_p, min_p, logit filter; SURVEY.md 2.2)")
+                                      "(device sampler: csrc/sampling.hip; SURVEY.md 2.2)")
         dev = _torch.device("cuda", _torch.cuda.current_device())
         x = logits.reshape(-1, logits.shape[-1]).to(dev, dtype=_torch.float32).contiguous()
         f = logit_filter.reshape(x.shape).to(dev).contiguous() if has_filter else None
-        tok = _torch.empty((x.shape[0],), dtype=_torch.int32, device=dev)
-        prob = _torch.empty((x.shape[0],), dtype=_torch.float32, device=dev)
-        _e.sample_rows(x, temperature, top_k, top_p, min_p, random, tok, prob, logit_filter=f)
+        rows = x.shape[0]
+        tok = _torch.empty((rows,), dtype=_torch.int32, device=dev)
+        prob = _torch.empty((rows,), dtype=_torch.float32, device=dev)
+        chain = (top_a > 0.0 or 0.0 < typical < 1.0 or bool(mirostat) or post_temperature != 1.0
+                 or max_temp > min_temp or smoothing_factor > 0.0 or skew != 0.0 or has_k)
+        if not chain:
+            _e.sample_rows(x, temperature, top_k, top_p, min_p, random, tok, prob, logit_filter=f)
+            mu_out = []
+        else:
+            kw = dict(top_a=top_a, tfs=tfs, typical=typical, post_temperature=post_temperature, min_temp=min_temp, max_temp=max_temp,
+                      temp_exponent=temp_exponent, smoothing_factor=smoothing_factor, skew=skew)
+            mu = kt = kp = None
+            if mirostat:
+                if len(mirostat_mu) < rows:
+                    raise RuntimeError("exllamav2_ext.sample_basic: mirostat_mu needs one value per row")
+                mu = _torch.tensor([float(m) for m in mirostat_mu[:rows]], dtype=_torch.float32, device=dev)
+                kw.update(mirostat=True, mirostat_tau=mirostat_tau, mirostat_eta=mirostat_eta, mirostat_mu=mu)
+            if has_k:
+                k = output_ktokens.shape[-1]
+                kt = _torch.empty((rows, k), dtype=_torch.int32, device=dev)
+                kp = _torch.empty((rows, k), dtype=_torch.float32, device=dev)
+                kw.update(out_ktokens=kt, out_kprobs=kp)
+            _e.sample_rows_chain(x, temperature, top_k, top_p, min_p, random, tok, prob, logit_filter=f, **kw)
+            if has_k:
+                output_ktokens.copy_(kt.to(output_ktokens.device, dtype=output_ktokens.dtype).view(output_ktokens.shape))
+                output_kprobs.copy_(kp.to(output_kprobs.device).view(output_kprobs.shape))
+            # (the reference returns its copy of the list with the rows' values updated: ext_sampling.cpp:286-289, 310)
+            mu_out = mu.cpu().tolist() + [float(m) for m in mirostat_mu[rows:]] if mirostat else []
         output_tokens.copy_(tok.to(output_tokens.device, dtype=output_tokens.dtype).view(output_tokens.shape))
         output_probs.copy_(prob.to(output_probs.device).view(output_probs.shape))
-        return []
+        return mu_out
     if mirostat or (xtc_probability and xtc_probability > 0.0):
         raise NotImplementedError("exllamav2_ext.sample_basic: mirostat / XTC are not built in this drop-in (SURVEY.md 2.2)")
     x = logits.reshape(-1, logits.shape[-1]).float()

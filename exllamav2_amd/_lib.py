@@ -20,6 +20,16 @@ ci = C.c_int
 cf = C.c_float
 cll = C.c_longlong
 
+class SampleChain(C.Structure):
+    """exl2_sample_chain (include/exl2_hip.h): the settings of the sampler chain's stages."""
+    _fields_ = [("top_a", cf), ("tfs", cf), ("typical", cf),
+                ("post_temperature", cf), ("min_temp", cf), ("max_temp", cf), ("temp_exponent", cf),
+                ("smoothing_factor", cf), ("skew", cf),
+                ("mirostat", ci), ("mirostat_tau", cf), ("mirostat_eta", cf),
+                ("num_probs", ci),
+                ("mirostat_mu", vp), ("out_ktokens", vp), ("out_kprobs", vp), ("out_counts", vp)]
+
+
 # name -> (restype, argtypes).  Every symbol declared in include/exl2_hip.h appears here (tests check both ways).
 PROTOTYPES = {
     "exl2_last_error": (C.c_char_p, []),
@@ -45,6 +55,9 @@ PROTOTYPES = {
     "exl2_sample_rows": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, cf, vp, vp, vp, vp]),
     "exl2_sample_rows_step": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
     "exl2_sample_rows_step2": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp]),
+    # (the settings record travels by address: SampleChain below)
+    "exl2_sample_rows_chain": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, cf, vp, vp, vp, vp, vp]),
+    "exl2_sample_rows_chain_step": (ci, [vp, ci, ci, ci, ci, vp, cf, ci, cf, cf, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, vp]),
     # sampler penalties + token bias (csrc/penalties.hip)
     "exl2_apply_penalties": (ci, [vp, ci, ci, ci, ci, vp, vp, ci, vp, ci, ci, vp, cf, ci, ci, cf, cf, vp, vp, vp]),
     # quantized KV cache

@@ -21,12 +21,19 @@
 //     an earlier stage left: the raw softmax probability of token k after top-k, or the first entry top-p dropped);
 //   * the random point is scaled by 0.9998 and, for rows after the first, advanced by the reference's recurrence
 //     (ext_sampling.cpp:273, 286-296).
+// The rest of sample_basic's chain -- quadratic-softmax smoothing, top-a, tfs, typical, mirostat, post-softmax / dynamic temperature,
+// skew, the top-token report -- is compiled only into the CHAIN instantiations of the kernel (exl2_sample_rows_chain / _chain_step);
+// the instantiations behind exl2_sample_rows / _step / _step2 carry none of it.  See "the chain stages" below.
 // Not built (the host refuses, never approximates): top_k = 0 or > 500 (the reference's quicksort regime has no defined tie
-// order), top-a, tfs, typical, mirostat, XTC, skew, smoothing, dynamic temperature, the top-token report.
+// order), XTC (xtc_cpu reads one entry past the candidates and compares an index with a probability: its result depends on stale
+// buffer contents), typical together with the top-token report (the reference then sorts only the reported entries and the pick
+// depends on its quicksort's partial order).
 #include "hw.h"
 #include "errors.h"
+#include "../../include/exl2_hip.h"
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #define SAMPLE_THREADS 1024
 #define SAMPLE_KMAX 500
@@ -49,6 +56,218 @@ struct SampleArgs
     // sampled as the reference's speculative verification does, by a sample() call of batch 1 with a fresh random.random()
     int per_row_random;
 };
+
+// The settings of the chain stages: exl2_sample_chain, the record the host fills -- ONE definition, the public header's (a neutral
+// record is all zeros except post_temperature = 1 and temp_exponent = 1) -- carried behind the arguments every instantiation takes.
+struct SampleChainArgs : SampleArgs { exl2_sample_chain c; };
+
+// ---- the chain stages (CHAIN instantiations only) -----------------------------------------------------------------------
+// They run on wave 0 like the stages above them: element-wise passes and the sorts on all 64 lanes, every sum that is compared
+// with a threshold by lane 0 in the reference's order.  p / ix: the candidate array in LDS; every lane calls with the same n.
+// Products that feed a sum are kept apart from it (the host code of the reference has no fused multiply-add).
+#define CHAIN_SWAP(p, ix, i, j) { const float tp_ = p[i]; p[i] = p[j]; p[j] = tp_; const int ti_ = ix[i]; ix[i] = ix[j]; ix[j] = ti_; }
+
+// keep_threshold (sampling.cpp:569-592) as one thread runs it, the n + 1 return included
+DEV int chain_keep_threshold(float* p, int* ix, int n, float thr)
+{
+    int i = 0, j = n - 1;
+    while (j >= i)
+    {
+        while (p[i] >= thr && j >= i) i++;
+        if (p[j] >= thr) { CHAIN_SWAP(p, ix, i, j); i++; }
+        j--;
+    }
+    return i;
+}
+
+// pre_sort_descending (sampling.cpp:399-421): entries below 1e-8 go behind the others by the reference's swaps (their order is
+// what a later walk over all n entries sees), lane 0; returns the number in front
+DEV int chain_presort(float* p, int* ix, int n)
+{
+    int i = 0;
+    if (lane_id() == 0)
+    {
+        int j = n - 1;
+        while (i <= j)
+        {
+            if (p[j] < 1e-8f) { j--; continue; }
+            if (p[i] >= 1e-8f) { i++; continue; }
+            CHAIN_SWAP(p, ix, i, j);
+            i++; j--;
+        }
+    }
+    i = (int)shfl_idx_u32((u32)i, 0);
+    wave_sync();
+    return i;
+}
+
+// Rank sort of (p, ix)[0 .. cnt) by key (descending, or ascending with ASC) into (tp, ti); equal keys by ascending token id, then
+// by position.  The reference's quicksort leaves equal keys in no defined order: parity is claimed where there are none.
+// key may be p itself.  BACK: the order is copied back over (p, ix).
+template <bool ASC, bool BACK>
+DEV void chain_rank_sort(const float* key, float* p, int* ix, float* tp, int* ti, int cnt)
+{
+    const int lane = lane_id();
+    for (int i = lane; i < cnt; i += 64)
+    {
+        const float k = key[i]; const int id = ix[i];
+        int rank = 0;
+        #pragma unroll 8
+        for (int j = 0; j < cnt; j++)
+        {
+            const float kj = key[j];
+            bool before = ASC ? kj < k : kj > k;
+            if (kj == k) { const int idj = ix[j]; before = idj < id || (idj == id && j < i); }
+            rank += before;
+        }
+        tp[rank] = p[i]; ti[rank] = id;
+    }
+    wave_sync();
+    if (BACK)
+    {
+        for (int i = lane; i < cnt; i += 64) { p[i] = tp[i]; ix[i] = ti[i]; }
+        wave_sync();
+    }
+}
+
+// sort_descending (sampling.cpp:424-440) with every entry in front sorted (max_index = n, or 0)
+DEV int chain_sort_desc(float* p, int* ix, float* tp, int* ti, int n)
+{
+    const int pre = chain_presort(p, ix, n);
+    chain_rank_sort<false, true>(p, p, ix, tp, ti, pre);
+    return pre;
+}
+
+// tfs_cpu (sampling.cpp:642-688); d: scratch for the second differences
+DEV int chain_tfs(float* p, int* ix, float* tp, int* ti, float* d, int n, float tfs)
+{
+    #pragma clang fp contract(off)
+    if (n < 3) return n;
+    const int nc = chain_sort_desc(p, ix, tp, ti, n);
+    for (int i = lane_id(); i < nc - 2; i += 64) d[i] = fabsf(-p[i] + 2.0f * p[i + 1] - p[i + 2]);
+    wave_sync();
+    int k = 0;
+    if (lane_id() == 0)
+    {
+        float dsum = 0.0f;
+        for (int i = 0; i < nc - 2; i++) dsum += d[i];
+        const float dsum_i = 1.0f / dsum;
+        float cumsum = 0.0f;
+        while (k < nc - 2)
+        {
+            const float q = d[k] * dsum_i;
+            cumsum += q;
+            if (cumsum > tfs) break;
+            k++;
+        }
+        k++;
+    }
+    k = (int)shfl_idx_u32((u32)k, 0);
+    wave_sync();
+    return k;
+}
+
+// typical_cpu (sampling.cpp:747-810); y: scratch for p + logf(p + 1e-10) and then | y - sum p y |
+DEV int chain_typical(float* p, int* ix, float* tp, int* ti, float* y, int n, float typical)
+{
+    #pragma clang fp contract(off)
+    const int r = chain_presort(p, ix, n);
+    for (int i = lane_id(); i < r; i += 64) { const float x = p[i]; y[i] = x + logf(x + 1e-10f); }
+    wave_sync();
+    float neg_entropy = 0.0f;
+    if (lane_id() == 0)
+        for (int i = 0; i < r; i++) { const float q = p[i] * y[i]; neg_entropy += q; }
+    neg_entropy = shfl_idx_f32(neg_entropy, 0);
+    for (int i = lane_id(); i < r; i += 64) y[i] = fabsf(y[i] - neg_entropy);
+    wave_sync();
+    chain_rank_sort<true, false>(y, p, ix, tp, ti, r);
+    int num = 0;
+    if (lane_id() == 0)
+    {
+        float cumprob = 0.0f;
+        while (true)
+        {
+            const float q = tp[num];
+            p[num] = q; ix[num] = ti[num];
+            cumprob += q;
+            if (cumprob >= typical) break;
+            num++;
+            if (num >= r) break;
+        }
+        if (num == 0) num = 1;
+    }
+    num = (int)shfl_idx_u32((u32)num, 0);
+    wave_sync();
+    return num;
+}
+
+// mirostat_pre_cpu (sampling.cpp:690-719): on the sorted array the first entry below 2^-mu is behind every entry at or above it
+DEV int chain_mirostat_pre(float* p, int* ix, float* tp, int* ti, int n, float mu, float tau)
+{
+    if (mu == 0.0f) mu = tau * 2.0f;
+    const int nc = chain_sort_desc(p, ix, tp, ti, n);
+    const float target = powf(2.0f, -mu);
+    u32 keep = 0;
+    for (int k = 1 + lane_id(); k < nc; k += 64) keep += p[k] >= target;
+    for (int mask = 1; mask < 64; mask <<= 1) keep += shfl_xor_u32(keep, mask);
+    return 1 + (int)keep;
+}
+
+// mirostat_post_cpu (sampling.cpp:721-745), one thread
+DEV float chain_mirostat_post(float mu, float tau, float eta, float p_chosen)
+{
+    #pragma clang fp contract(off)
+    if (mu == 0.0f) mu = tau * 2.0f;
+    const float observed_surprise = -log2f(p_chosen);
+    const float step = eta * (tau - observed_surprise);
+    return mu + step;
+}
+
+// post_softmax_temperature (sampling.cpp:195-262) up to its normalisation (the caller's: the same sequential sum and reciprocal);
+// e: scratch for the entropy terms
+DEV void chain_post_temperature(float* p, float* e, int n, float temperature, float min_temp, float max_temp, float temp_exponent)
+{
+    #pragma clang fp contract(off)
+    if (max_temp > min_temp)
+    {
+        for (int i = lane_id(); i < n; i += 64) { const float q = p[i]; e[i] = q > 0.0f ? q * logf(q) : 0.0f; }
+        wave_sync();
+        if (lane_id() == 0)
+        {
+            float entropy = 0.0f;
+            for (int i = 0; i < n; i++) if (p[i] > 0.0f) entropy -= e[i];
+            float max_entropy = -logf(1.0f / (float)n);
+            if (max_entropy == 0.0f) max_entropy = 1.0f;
+            const float scaled = (max_temp - min_temp) * powf(entropy / max_entropy, temp_exponent);
+            temperature = min_temp + scaled;
+        }
+        temperature = shfl_idx_f32(temperature, 0);
+    }
+    const float itemp = 1.0f / temperature;
+    for (int i = lane_id(); i < n; i += 64) p[i] = powf(p[i], itemp);
+    wave_sync();
+}
+
+// the top-token report (ext_sampling.cpp:244-268), one thread: the sorted candidates up to the first zero probability, then the
+// reference's filler ids exactly as its loop runs (after a collision the rescan resumes at candidate 1)
+DEV void chain_report(const float* p, const int* ix, int n, int num_probs, int* out_ktokens, float* out_kprobs)
+{
+    int j = 0;
+    for (; j < n && j < num_probs; ++j)
+    {
+        const float q = p[j];
+        if (q == 0.0f) break;
+        out_ktokens[j] = ix[j]; out_kprobs[j] = q;
+    }
+    int fake_idx = 0;
+    for (; j < num_probs; ++j)
+    {
+        for (int k = 0; k < n; ++k)
+            if (ix[k] == fake_idx) { fake_idx++; k = 0; }
+        out_ktokens[j] = fake_idx; out_kprobs[j] = 0.0f;
+        fake_idx++;
+    }
+}
 
 // Row walks.  A row whose length and stride are multiples of 4 elements on a 16-byte-aligned base (every real vocabulary) is
 // walked in quads -- 16-byte (fp32) / 8-byte (fp16) accesses, four independent loads in flight per thread: one workgroup owns
@@ -116,8 +335,9 @@ DEV u32 wave_scan_incl(u32 v)
 // cost no memory pass at all; the probabilities are written to the workspace once (the later stages and the caller read them
 // there).  Same element -> thread assignment and the same operation order as the memory walks: results identical bit for bit.
 #define SAMPLE_REG_QUADS 8
-template <typename T, bool REG>
-KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
+// CHAIN: the chain stages above at the reference's positions; false compiles none of them (and takes the plain arguments)
+template <typename T, bool REG, bool CHAIN>
+KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(std::conditional_t<CHAIN, SampleChainArgs, SampleArgs> a)
 {
     SHARED float red_v[16];
     SHARED int   red_i[16];
@@ -181,7 +401,18 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
     block_sync();
 
     // ---- 2. e = expf((l - max) / T), sum, p = e / sum ------------------------------------------------------------------
-    const float itemp = 1.0f / a.temperature;
+    float temperature = a.temperature;
+    bool smooth = false;
+    if constexpr (CHAIN)
+    {
+        // smoothing_factor (ext_sampling.cpp:155-160, sampling.cpp:143-145): l = -(l - max)^2, and `temperature /= smoothing_factor`
+        // INSIDE the reference's batch loop -- row r of a call sees the temperature divided r + 1 times.  Rows with their own random
+        // points (per_row_random) are batch-1 calls of the reference, each with the caller's temperature: divided once.
+        smooth = a.c.smoothing_factor > 0.0f;
+        if (smooth) for (int r = 0; r <= (a.per_row_random ? 0 : row); r++) temperature /= a.c.smoothing_factor;
+    }
+    auto shaped = [&](float l) { if constexpr (CHAIN) { if (smooth) l *= -l; } return l; };
+    const float itemp = 1.0f / temperature;
     float part = 0.0f;
     if constexpr (REG)
     {
@@ -191,7 +422,7 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
             if (t + u * SAMPLE_THREADS < nq_reg)
             {
                 #pragma unroll
-                for (int c = 0; c < 4; c++) { const float x = expf((pr[u][c] - maxl) * itemp); part += x; pr[u][c] = x; }
+                for (int c = 0; c < 4; c++) { const float x = expf(shaped(pr[u][c] - maxl) * itemp); part += x; pr[u][c] = x; }
             }
         }
     }
@@ -206,7 +437,7 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
             for (int c = 0; c < 4; c++)
             {
                 float x = 0.0f;
-                if (!fr || fr[4 * q + c]) { x = expf((l[c] - maxl) * itemp); part += x; }
+                if (!fr || fr[4 * q + c]) { x = expf(shaped(l[c] - maxl) * itemp); part += x; }
                 e[c] = x;
             }
             *(f32x4*)(ws + 4 * (size_t)q) = e;
@@ -215,7 +446,7 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
     else for (int i = t; i < V; i += SAMPLE_THREADS)
     {
         float e = 0.0f;
-        if (!fr || fr[i]) { e = expf(((float)lr[i] - maxl) * itemp); part += e; }
+        if (!fr || fr[i]) { e = expf(shaped((float)lr[i] - maxl) * itemp); part += e; }
         ws[i] = e;
     }
     for (int mask = 1; mask < 64; mask <<= 1) part += shfl_xor_f32(part, mask);
@@ -260,6 +491,21 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
             const float p = ws[maxi];
             a.out_tokens[row] = maxi;
             a.out_probs[row] = p * (1.0f / p);
+            if constexpr (CHAIN)
+            {
+                // one candidate: every stage of the chain passes it through; the report and mirostat's update still run
+                const float p1 = p * (1.0f / p);
+                if (a.c.out_counts) a.c.out_counts[row] = 1;
+                if (a.c.num_probs)
+                    chain_report(&p1, &maxi, 1, a.c.num_probs, a.c.out_ktokens + (size_t)row * a.c.num_probs, a.c.out_kprobs + (size_t)row * a.c.num_probs);
+                if (a.c.mirostat) a.c.mirostat_mu[row] = chain_mirostat_post(a.c.mirostat_mu[row], a.c.mirostat_tau, a.c.mirostat_eta, p1);
+                if (a.hist_pos)
+                {
+                    const int pos = a.hist_pos[row] + a.pos_inc;
+                    if (a.history) a.history[(size_t)row * a.hist_stride + pos] = maxi;
+                    if (a.pos_inc) a.hist_pos[row] = pos;
+                }
+            }
         }
         return;
     }
@@ -447,7 +693,18 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
             cand_p[rank] = p; cand_i[rank] = ix;
         }
     }
-    if (t == SAMPLE_THREADS - 1) { cand_p[K] = ws[K]; cand_i[K] = K; cand_p[K + 1] = 0.0f; cand_i[K + 1] = 0; }
+    if constexpr (CHAIN)
+    {
+        // up to three keep_threshold calls (top-a, min-p) can each hand back n + 1: positions K .. K + 2 hold what the reference's
+        // buffer holds there (the raw softmax probabilities; past the vocabulary the reference reads outside its buffer: zeros here)
+        if (t == SAMPLE_THREADS - 1)
+            for (int e = 0; e < 4; e++)
+            {
+                const int pos = K + e; const bool in = e < 3 && pos < V;
+                cand_p[pos] = in ? ws[pos] : 0.0f; cand_i[pos] = in ? pos : 0;
+            }
+    }
+    else if (t == SAMPLE_THREADS - 1) { cand_p[K] = ws[K]; cand_i[K] = K; cand_p[K + 1] = 0.0f; cand_i[K + 1] = 0; }
     block_sync();
     if (wave_id() != 0) return;
     // (wave 0 stays: lane 0 runs the reference's sequential sums and walks, the element-wise passes between them use all 64 lanes)
@@ -525,6 +782,21 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
         n = top;
         normalize(n);
     }
+    if constexpr (CHAIN)
+    {
+        if (n > 1 && a.c.top_a > 0.0f)                              // sampling.cpp:594-617: threshold top_a * top^2
+        {
+            if (lead)
+            {
+                float topv = cand_p[0];
+                for (int i = 1; i < n; i++) if (cand_p[i] > topv) topv = cand_p[i];
+                n = chain_keep_threshold(cand_p, cand_i, n, a.c.top_a * topv * topv);
+            }
+            n = (int)shfl_idx_u32((u32)n, 0);
+            wave_sync();
+            normalize(n);
+        }
+    }
     if (n > 1 && a.min_p > 0.0f && a.min_p < 1.0f)                  // sampling.cpp:620-640 + keep_threshold :569-592
     {
         if (lead)
@@ -550,6 +822,26 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
         wave_sync();
         normalize(n);
     }
+    float mu_in = 0.0f;
+    if constexpr (CHAIN)
+    {
+        // (scratch: the quick select's list is free once the candidates stand)
+        float* scratch = (float*)lst_k;
+        if (n > 1 && a.c.tfs > 0.0f && a.c.tfs < 1.0f) { n = chain_tfs(cand_p, cand_i, stk_p, stk_i, scratch, n, a.c.tfs); normalize(n); }
+        if (n > 1 && a.c.typical > 0.0f && a.c.typical < 1.0f) { n = chain_typical(cand_p, cand_i, stk_p, stk_i, scratch, n, a.c.typical); normalize(n); }
+        if (a.c.mirostat) mu_in = a.c.mirostat_mu[row];
+        if (n > 1 && a.c.mirostat) { n = chain_mirostat_pre(cand_p, cand_i, stk_p, stk_i, n, mu_in, a.c.mirostat_tau); normalize(n); }
+        if (n > 1 && (a.c.post_temperature != 1.0f || a.c.max_temp > a.c.min_temp))
+        {
+            chain_post_temperature(cand_p, scratch, n, a.c.post_temperature, a.c.min_temp, a.c.max_temp, a.c.temp_exponent);
+            normalize(n);
+        }
+        // ext_sampling.cpp:239-268: the candidates in descending order for the report and for a skewed pick (num_candidates keeps
+        // counting the entries below 1e-8 behind them)
+        if (a.c.num_probs || a.c.skew != 0.0f) chain_sort_desc(cand_p, cand_i, stk_p, stk_i, n);
+        if (lead && a.c.num_probs)
+            chain_report(cand_p, cand_i, n, a.c.num_probs, a.c.out_ktokens + (size_t)row * a.c.num_probs, a.c.out_kprobs + (size_t)row * a.c.num_probs);
+    }
     if (!lead) return;
     const unsigned ctr = a.randoms ? (unsigned)a.counter[0] + (a.per_row_random ? (unsigned)row : 0u) : 0u;
     float random = a.randoms ? a.randoms[ctr % (unsigned)a.n_randoms] : a.random;
@@ -559,7 +851,9 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
         for (int j = 0; j < 10; j++) { x = (float)((double)x + (1.337 + (double)random)); x *= x; x = fmodf(x, 1.0f); }
         random = x;
     }
-    const float radj = (float)((double)random * 0.9998);            // :273
+    float random_s = random;
+    if constexpr (CHAIN) { if (a.c.skew != 0.0f) random_s = powf(random, expf(-a.c.skew)); }      // :272-275
+    const float radj = (float)((double)random_s * 0.9998);          // :279
     int idx = 0;
     float accum = 0.0f;
     bool done = false;
@@ -578,6 +872,11 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
     }
     a.out_tokens[row] = cand_i[idx];
     a.out_probs[row] = cand_p[idx];
+    if constexpr (CHAIN)
+    {
+        if (a.c.mirostat) a.c.mirostat_mu[row] = chain_mirostat_post(mu_in, a.c.mirostat_tau, a.c.mirostat_eta, cand_p[idx]);
+        if (a.c.out_counts) a.c.out_counts[row] = n;
+    }
     if (a.hist_pos)
     {
         const int pos = a.hist_pos[row] + a.pos_inc;
@@ -586,9 +885,8 @@ KERNEL void __launch_bounds__(SAMPLE_THREADS) sample_rows_kernel(SampleArgs a)
     }
 }
 
-extern "C" {
-
-static int sample_launch(SampleArgs a, int logits_f32, int rows, float random, void* stream)
+template <bool CHAIN, typename Args>
+static int sample_launch(Args a, int logits_f32, int rows, float random, void* stream)
 {
     EXL2_REQUIRE(a.logits && a.out_tokens && a.out_probs && a.ws, "sample_rows: null argument");
     EXL2_REQUIRE(a.vocab >= 2 && a.ld >= a.vocab, "sample_rows: vocab %d, row stride %d", a.vocab, a.ld);
@@ -606,13 +904,15 @@ static int sample_launch(SampleArgs a, int logits_f32, int rows, float random, v
     const bool reg = reg_on && vec && !a.filter && a.vocab <= 4 * SAMPLE_REG_QUADS * SAMPLE_THREADS;
     a.quick = 1;
     if (const char* e = getenv("EXL2_SAMPLE_QUICK")) a.quick = atoi(e);
-    if (logits_f32) { if (reg) LAUNCH((sample_rows_kernel<float, true>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a);
-                      else     LAUNCH((sample_rows_kernel<float, false>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a); }
-    else            { if (reg) LAUNCH((sample_rows_kernel<f16, true>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a);
-                      else     LAUNCH((sample_rows_kernel<f16, false>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a); }
+    if (logits_f32) { if (reg) LAUNCH((sample_rows_kernel<float, true, CHAIN>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a);
+                      else     LAUNCH((sample_rows_kernel<float, false, CHAIN>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a); }
+    else            { if (reg) LAUNCH((sample_rows_kernel<f16, true, CHAIN>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a);
+                      else     LAUNCH((sample_rows_kernel<f16, false, CHAIN>), dim3((unsigned)rows), dim3(SAMPLE_THREADS), 0, stream, a); }
     HIP_TRY(hipGetLastError());
     return EXL2_OK;
 }
+
+extern "C" {
 
 int exl2_sample_rows(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
                      float temperature, int top_k, float top_p, float min_p, float random,
@@ -623,7 +923,7 @@ int exl2_sample_rows(const void* logits, int logits_f32, int rows, int vocab, in
     a.logits = logits; a.ld = ld; a.vocab = vocab; a.filter = (const u8*)logit_filter;
     a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.min_p = min_p;
     a.out_tokens = out_tokens; a.out_probs = out_probs; a.ws = workspace;
-    return sample_launch(a, logits_f32, rows, random, stream);
+    return sample_launch<false>(a, logits_f32, rows, random, stream);
 }
 
 // The same sampler as the last launch of a decode-step graph: the random point of the step is randoms[*counter % n_randoms]
@@ -647,7 +947,7 @@ static int sample_step(const void* logits, int logits_f32, int rows, int vocab, 
     a.out_tokens = out_tokens; a.out_probs = out_probs; a.ws = workspace;
     a.randoms = randoms; a.n_randoms = n_randoms; a.counter = counter; a.per_row_random = per_row_random ? 1 : 0;
     a.history = history; a.hist_pos = hist_pos; a.hist_stride = hist_stride; a.pos_inc = pos_inc;
-    return sample_launch(a, logits_f32, rows, 0.0f, stream);
+    return sample_launch<false>(a, logits_f32, rows, 0.0f, stream);
 }
 
 int exl2_sample_rows_step(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
@@ -668,6 +968,62 @@ int exl2_sample_rows_step2(const void* logits, int logits_f32, int rows, int voc
 {
     return sample_step(logits, logits_f32, rows, vocab, ld, logit_filter, temperature, top_k, top_p, min_p, randoms, n_randoms, counter,
                        per_row_random, out_tokens, out_probs, workspace, history, hist_pos, hist_stride, pos_inc, stream);
+}
+
+// ---- the whole chain (exl2_sample_rows_chain / _chain_step): the arguments of exl2_sample_rows / _step2 + the settings record ----
+static int chain_check(const exl2_sample_chain* c, float temperature, int top_k)
+{
+    EXL2_REQUIRE(c, "sample_rows_chain: null settings record");
+    EXL2_REQUIRE(c->num_probs >= 0 && c->num_probs <= 32, "sample_rows_chain: num_probs %d outside [0, 32]", c->num_probs);
+    EXL2_REQUIRE(!c->num_probs || (c->out_ktokens && c->out_kprobs), "sample_rows_chain: num_probs %d without out_ktokens / out_kprobs", c->num_probs);
+    EXL2_REQUIRE(c->top_a >= 0.0f, "sample_rows_chain: top_a %f is negative", (double)c->top_a);
+    EXL2_REQUIRE(c->tfs >= 0.0f && c->tfs <= 1.0f, "sample_rows_chain: tfs %f outside [0, 1]", (double)c->tfs);
+    EXL2_REQUIRE(c->typical >= 0.0f && c->typical <= 1.0f, "sample_rows_chain: typical %f outside [0, 1]", (double)c->typical);
+    EXL2_REQUIRE(c->smoothing_factor >= 0.0f, "sample_rows_chain: smoothing_factor %f is negative", (double)c->smoothing_factor);
+    EXL2_REQUIRE(c->max_temp > c->min_temp || c->post_temperature > 0.0f, "sample_rows_chain: post_temperature %f is not positive",
+                 (double)c->post_temperature);
+    EXL2_REQUIRE(!c->mirostat || c->mirostat_mu, "sample_rows_chain: mirostat without a mirostat_mu buffer");
+    const bool greedy = temperature < 0.01f || top_k == 1;
+    if (!greedy && c->num_probs > 0 && c->typical > 0.0f && c->typical < 1.0f)
+        EXL2_FAIL(EXL2_E_UNSUPPORTED, "sample_rows_chain: typical together with the top-token report is refused: the reference then sorts only the "
+                  "first num_probs entries and the pick depends on its quicksort's partial order");
+    return EXL2_OK;
+}
+
+int exl2_sample_rows_chain(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                           float temperature, int top_k, float top_p, float min_p, float random, const exl2_sample_chain* chain,
+                           int* out_tokens, float* out_probs, float* workspace, void* stream)
+{
+    if (const int rc = chain_check(chain, temperature, top_k)) return rc;
+    SampleChainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = logits; a.ld = ld; a.vocab = vocab; a.filter = (const u8*)logit_filter;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.min_p = min_p;
+    a.out_tokens = out_tokens; a.out_probs = out_probs; a.ws = workspace;
+    a.c = *chain;
+    return sample_launch<true>(a, logits_f32, rows, random, stream);
+}
+
+// exl2_sample_rows_step2 with the chain: mirostat_mu is read and written by the launch, the top tokens go to out_ktokens /
+// out_kprobs -- nothing of the launch changes from token to token, so the step replays from one graph
+int exl2_sample_rows_chain_step(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                                float temperature, int top_k, float top_p, float min_p,
+                                const float* randoms, int n_randoms, const int* counter, int per_row_random,
+                                const exl2_sample_chain* chain, int* out_tokens, float* out_probs, float* workspace,
+                                int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream)
+{
+    if (const int rc = chain_check(chain, temperature, top_k)) return rc;
+    EXL2_REQUIRE(randoms && counter && n_randoms >= 1, "sample_rows_chain_step: random buffer / counter missing");
+    EXL2_REQUIRE(!history || hist_pos, "sample_rows_chain_step: history needs hist_pos");
+    SampleChainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = logits; a.ld = ld; a.vocab = vocab; a.filter = (const u8*)logit_filter;
+    a.temperature = temperature; a.top_k = top_k; a.top_p = top_p; a.min_p = min_p;
+    a.out_tokens = out_tokens; a.out_probs = out_probs; a.ws = workspace;
+    a.randoms = randoms; a.n_randoms = n_randoms; a.counter = counter; a.per_row_random = per_row_random ? 1 : 0;
+    a.history = history; a.hist_pos = hist_pos; a.hist_stride = hist_stride; a.pos_inc = pos_inc;
+    a.c = *chain;
+    return sample_launch<true>(a, logits_f32, rows, 0.0f, stream);
 }
 
 }  // extern "C"

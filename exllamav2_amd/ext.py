@@ -1140,6 +1140,92 @@ class ExtC:
         else:
             self.lib.check(self.lib.exl2_sample_rows_step(*args, *tail))
 
+    CHAIN_DEFAULTS = {"top_a": 0.0, "tfs": 0.0, "typical": 0.0, "post_temperature": 1.0, "min_temp": 0.0, "max_temp": 0.0,
+                      "temp_exponent": 1.0, "smoothing_factor": 0.0, "skew": 0.0, "mirostat": False, "mirostat_tau": 0.0,
+                      "mirostat_eta": 0.0, "xtc_probability": 0.0, "mirostat_mu": None, "out_ktokens": None, "out_kprobs": None, "out_counts": None}
+
+    def _chain_record(self, rows: int, chain: dict):
+        """exl2_sample_chain from keywords (CHAIN_DEFAULTS: the reference's sample_basic argument names; mirostat_mu fp32 [rows],
+        out_ktokens int32 / out_kprobs fp32 [rows, num_probs] device tensors).  num_probs is out_ktokens' last dimension."""
+        from ._lib import SampleChain
+        unknown = set(chain) - set(self.CHAIN_DEFAULTS)
+        if unknown:
+            raise TypeError(f"sample_rows_chain: unknown setting(s) {sorted(unknown)}")
+        st = self.CHAIN_DEFAULTS | chain
+        if st["xtc_probability"] and float(st["xtc_probability"]) > 0.0:
+            raise RuntimeError("sample_rows_chain: XTC is refused: the reference's xtc_cpu reads one entry past the candidates and compares "
+                               "an index with a probability, so its result depends on stale buffer contents -- there is no defined "
+                               "behaviour to match")
+        mu, kt, kp = st["mirostat_mu"], st["out_ktokens"], st["out_kprobs"]
+        num_probs = 0
+        if not _is_none(kt):
+            num_probs = kt.shape[-1]
+            if _is_none(kp) or kt.numel() != rows * num_probs or kp.numel() != rows * num_probs:
+                raise RuntimeError("sample_rows_chain: out_ktokens / out_kprobs must both be [rows, num_probs]")
+        if not _is_none(mu) and mu.numel() < rows:
+            raise RuntimeError("sample_rows_chain: mirostat_mu must hold one value per row")
+        if not _is_none(st["out_counts"]) and st["out_counts"].numel() < rows:
+            raise RuntimeError("sample_rows_chain: out_counts must hold one value per row")
+        rec = SampleChain(float(st["top_a"]), float(st["tfs"]), float(st["typical"]), float(st["post_temperature"]),
+                          float(st["min_temp"]), float(st["max_temp"]), float(st["temp_exponent"]), float(st["smoothing_factor"]),
+                          float(st["skew"]), int(bool(st["mirostat"])), float(st["mirostat_tau"]), float(st["mirostat_eta"]),
+                          int(num_probs),
+                          self._ptr(mu, torch.float32, "mirostat_mu"), self._ptr(kt, torch.int32, "out_ktokens"),
+                          self._ptr(kp, torch.float32, "out_kprobs"), self._ptr(st["out_counts"], torch.int32, "out_counts"))
+        return rec
+
+    def sample_rows_chain(self, logits, temperature: float, top_k: int, top_p: float, min_p: float, random: float,
+                          out_tokens, out_probs, logit_filter=None, workspace=None, vocab: int | None = None, **chain):
+        """sample_rows with the rest of the reference's sampler chain (include/exl2_hip.h exl2_sample_rows_chain): chain takes the
+        names of CHAIN_DEFAULTS -- top_a, tfs, typical, post_temperature, min_temp, max_temp, temp_exponent, smoothing_factor, skew,
+        mirostat (+ mirostat_tau, mirostat_eta, mirostat_mu: fp32 [rows] device tensor, updated in place), out_ktokens int32 /
+        out_kprobs fp32 [rows, num_probs] (the top-token report), out_counts int32 [rows] (candidates the pick was made from).  All neutral: sample_rows, bit for bit.  Returns the workspace."""
+        import ctypes
+        ld = logits.shape[-1]
+        rows = logits.numel() // ld
+        v = int(vocab or ld)
+        if logits.dtype not in (torch.float16, torch.float32):
+            raise RuntimeError(f"sample_rows_chain: logits must be fp16 or fp32, got {logits.dtype}")
+        if workspace is None:
+            workspace = torch.empty((rows, v), dtype=torch.float32, device=logits.device)
+        if workspace.numel() < rows * v:
+            raise RuntimeError("sample_rows_chain: workspace smaller than rows x vocab")
+        f = None
+        if not _is_none(logit_filter):
+            f = logit_filter.view(torch.uint8) if logit_filter.dtype == torch.bool else logit_filter
+            if f.numel() != rows * v:
+                raise RuntimeError("sample_rows_chain: logit_filter must be [rows, vocab]")
+        rec = self._chain_record(rows, chain)
+        self.lib.check(self.lib.exl2_sample_rows_chain(self._ptr(logits, None, "logits"), int(logits.dtype == torch.float32), rows, v, ld,
+                                                       self._ptr(f, torch.uint8, "logit_filter"), float(temperature), int(top_k),
+                                                       float(top_p), float(min_p), float(random), ctypes.addressof(rec),
+                                                       self._ptr(out_tokens, torch.int32, "out_tokens"),
+                                                       self._ptr(out_probs, torch.float32, "out_probs"),
+                                                       self._ptr(workspace, torch.float32, "workspace"), self._stream(logits)))
+        return workspace
+
+    def sample_rows_chain_step(self, logits, temperature: float, top_k: int, top_p: float, min_p: float, randoms, counter,
+                               out_tokens, out_probs, workspace, history, hist_pos, pos_inc: int = 1, vocab: int | None = None,
+                               per_row_random: bool = False, **chain) -> None:
+        """sample_rows_step with the chain (exl2_sample_rows_chain_step): mirostat_mu and the top-token outputs are device tensors
+        the launch reads and writes, so a captured step replays without host traffic."""
+        import ctypes
+        ld = logits.shape[-1]
+        rows = logits.numel() // ld
+        v = int(vocab or ld)
+        if workspace.numel() < rows * v:
+            raise RuntimeError("sample_rows_chain_step: workspace smaller than rows x vocab")
+        rec = self._chain_record(rows, chain)
+        self.lib.check(self.lib.exl2_sample_rows_chain_step(
+            self._ptr(logits, None, "logits"), int(logits.dtype == torch.float32), rows, v, ld, None,
+            float(temperature), int(top_k), float(top_p), float(min_p),
+            self._ptr(randoms, torch.float32, "randoms"), randoms.numel(), self._ptr(counter, torch.int32, "counter"),
+            int(bool(per_row_random)), ctypes.addressof(rec),
+            self._ptr(out_tokens, torch.int32, "out_tokens"), self._ptr(out_probs, torch.float32, "out_probs"),
+            self._ptr(workspace, torch.float32, "workspace"), self._ptr(history, torch.int32, "history"),
+            self._ptr(hist_pos, torch.int32, "hist_pos"), 0 if _is_none(history) else history.shape[-1], int(pos_inc),
+            self._stream(logits)))
+
     @staticmethod
     def penalty_ramps(penalty: float, decay: int, alpha_frequency: float, alpha_presence: float):
         """The values of the three penalties inside the decay range, as apply_rep_penalty_cpu reaches them (cpp/sampling.cpp:54-62,

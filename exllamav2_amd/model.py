@@ -572,9 +572,61 @@ class GreedyGraphDecoder:
             ext.argmax_rows(self.logits, self.ids, cfg.vocab_size, self.history, self.cache_seqlens, pos_inc=1)
             return
         logits = self._penalised_logits(sm)
-        ext.sample_rows_step(logits, sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"], sm["randoms"], sm["counter"],
-                             self.ids, sm["probs"], sm["ws"], self.history, self.cache_seqlens, pos_inc=1, vocab=cfg.vocab_size)
+        ch = sm.get("chain")
+        if ch is None:
+            ext.sample_rows_step(logits, sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"], sm["randoms"], sm["counter"],
+                                 self.ids, sm["probs"], sm["ws"], self.history, self.cache_seqlens, pos_inc=1, vocab=cfg.vocab_size)
+        else:
+            ext.sample_rows_chain_step(logits, ch["temperature"], sm["top_k"], sm["top_p"], sm["min_p"], sm["randoms"], sm["counter"],
+                                       self.ids, sm["probs"], sm["ws"], self.history, self.cache_seqlens, pos_inc=1,
+                                       vocab=cfg.vocab_size, **ch["kw"])
         ext.add_i32_(sm["counter"], 1)
+
+    # ---- the rest of the reference sampler's chain (sampler.py:54-110 Settings names), on the device: csrc/sampling.hip CHAIN -------
+    CHAIN_DEFAULTS = {"top_a": 0.0, "tfs": 0.0, "typical": 0.0, "temperature_last": False, "smoothing_factor": 0.0, "min_temp": 0.0,
+                      "max_temp": 0.0, "temp_exponent": 1.0, "skew": 0.0, "mirostat": False, "mirostat_tau": 1.5,
+                      "mirostat_eta": 0.1, "return_top_tokens": 0}
+
+    def _split_settings(self, kw: dict):
+        """(chain settings, penalty settings) of the keywords of a sampled run"""
+        chain = {k: v for k, v in kw.items() if k in self.CHAIN_DEFAULTS}
+        return chain, {k: v for k, v in kw.items() if k not in self.CHAIN_DEFAULTS}
+
+    def _chain_state(self, kw: dict, temperature: float, old=None):
+        """The chain settings of a sampled run as what the launch needs: None when all of them are neutral -- the sampled step is
+        then exactly the launch without them.  temperature_last moves the temperature behind the truncation stages like
+        sampler.py:540-559 does (softmax at 1, post-softmax temperature = the setting).  mu lives in `self.mirostat_mu` (fp32 [batch],
+        0 = not yet initialised), the top tokens and their probabilities of the LAST sampled step in `self.top_tokens` /
+        `self.top_probs` ([batch, return_top_tokens]): a report needs the step it is made for, and a captured step can only write
+        to addresses fixed at capture.  `old`: a state (the captured step's) that is returned as it is when its settings are these --
+        its buffers are the ones the captured launch writes, and `top_tokens` / `top_probs` point at them again."""
+        st = self.CHAIN_DEFAULTS | kw
+        K = int(st["return_top_tokens"])
+        key = (float(st["top_a"]), float(st["tfs"]), float(st["typical"]), bool(st["temperature_last"]), float(st["smoothing_factor"]),
+               float(st["min_temp"]), float(st["max_temp"]), float(st["temp_exponent"]), float(st["skew"]), bool(st["mirostat"]),
+               float(st["mirostat_tau"]), float(st["mirostat_eta"]), K)
+        active = (key[0] > 0 or 0 < key[1] < 1 or 0 < key[2] < 1 or (key[3] and float(temperature) != 1.0) or key[4] > 0
+                  or key[6] > key[5] or key[8] != 0 or key[9] or K > 0)
+        if not active:
+            return None
+        if old is not None and old["key"] == key + (float(temperature),):
+            if "out_ktokens" in old["kw"]:
+                self.top_tokens, self.top_probs = old["kw"]["out_ktokens"], old["kw"]["out_kprobs"]
+            return old
+        dev = self.logits.device
+        kwargs = {"top_a": key[0], "tfs": key[1], "typical": key[2], "post_temperature": float(temperature) if key[3] else 1.0,
+                  "min_temp": key[5], "max_temp": key[6], "temp_exponent": key[7], "smoothing_factor": key[4], "skew": key[8],
+                  "mirostat": key[9], "mirostat_tau": key[10], "mirostat_eta": key[11]}
+        if key[9]:
+            if getattr(self, "mirostat_mu", None) is None:
+                self.mirostat_mu = torch.zeros((self.b,), dtype=torch.float32, device=dev)
+            kwargs["mirostat_mu"] = self.mirostat_mu
+        if K > 0:
+            if getattr(self, "top_tokens", None) is None or self.top_tokens.shape[-1] != K:
+                self.top_tokens = torch.zeros((self.b, K), dtype=torch.int32, device=dev)
+                self.top_probs = torch.zeros((self.b, K), dtype=torch.float32, device=dev)
+            kwargs["out_ktokens"], kwargs["out_kprobs"] = self.top_tokens, self.top_probs
+        return {"key": key + (float(temperature),), "temperature": 1.0 if key[3] else float(temperature), "kw": kwargs}
 
     # ---- the reference sampler's penalties and token bias (sampler.py:408-429), on the device: csrc/penalties.hip --------------
     PENALTY_DEFAULTS = {"token_repetition_penalty": 1.0, "token_repetition_range": -1, "token_repetition_decay": 0,
@@ -846,23 +898,29 @@ class GreedyGraphDecoder:
                 self.stream.wait_event(self.chain["ev_b"])
 
     def capture_sampled(self, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0, n_randoms: int = 4096,
-                        **penalties):
+                        **settings):
         """A second step graph whose last launches are the device sampler (exl2_sample_rows_step) + its counter increment instead
         of the arg-max: `run_sampled` with these settings then replays ONE graph per token -- the random points are read from a
         device buffer the host fills before the run (n_randoms tokens ahead at most per fill).
         penalties: token_repetition_penalty / _range / _decay, token_frequency_penalty, token_presence_penalty, token_bias (fp32
         [vocab]) -- the reference Settings' names and meaning (sampler.py:54-69, 408-429).  Any of them off its neutral value puts
-        exl2_apply_penalties in front of the sampler, inside the same graph."""
+        exl2_apply_penalties in front of the sampler, inside the same graph.
+        The rest of the reference's chain by its Settings' names -- top_a, tfs, typical, temperature_last, smoothing_factor, min_temp,
+        max_temp, temp_exponent, skew, mirostat, mirostat_tau, mirostat_eta, return_top_tokens: any of them off its neutral value
+        makes the sampler launch exl2_sample_rows_chain_step (all neutral: the same launches as without them).  `mirostat_mu` is reset
+        here; `top_tokens` / `top_probs` hold the report of the last step."""
         ext, cfg = self.model.ext, self.model.config
         if self._overlapped():
             raise RuntimeError("capture_sampled: not available on the experimental overlapped chain")
         dev = self.logits.device
+        chain_kw, penalties = self._split_settings(settings)
         sm = {"temperature": float(temperature), "top_k": int(top_k), "top_p": float(top_p), "min_p": float(min_p),
               "randoms": torch.zeros((int(n_randoms),), dtype=torch.float32, device=dev),
               "counter": torch.zeros((1,), dtype=torch.int32, device=dev),
               "probs": torch.zeros((self.b,), dtype=torch.float32, device=dev),
               "ws": torch.empty((self.b, cfg.vocab_size), dtype=torch.float32, device=dev)}
         sm["pen"] = self._penalty_state(penalties)
+        sm["chain"] = self._chain_state(chain_kw, temperature)
         sm["graph"] = None
         if dev.type == "cuda":
             greedy_graph, self.graph = self.graph, None
@@ -874,6 +932,8 @@ class GreedyGraphDecoder:
                 self.graph = greedy_graph
                 self._sampling = None
         sm["counter"].zero_()
+        if getattr(self, "mirostat_mu", None) is not None:
+            self.mirostat_mu.zero_()                              # (the warm-up steps of the capture have sampled: mu starts over)
         old = getattr(self, "_sampled", None)
         if old is not None and old.get("graph") is not None:
             ext.graph_free(old["graph"])                          # a re-capture with new settings replaces the old sampled graph
@@ -881,15 +941,18 @@ class GreedyGraphDecoder:
         return self
 
     def run_sampled(self, n_tokens: int, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0,
-                    randoms=None, seed: int = 0, use_graph: bool = True, **penalties):
+                    randoms=None, seed: int = 0, use_graph: bool = True, **settings):
         """Decode `n_tokens` tokens per sequence with the DEVICE sampler (csrc/sampling.hip; the reference's sample_basic for
         these settings: ext_sampling.cpp:93-301) instead of the arg-max: per token the step's graph, then one
         `sample_rows` launch on the step's logits that overwrites the token fed to the next step, then the token log.
         The only thing the host supplies per token is the random point (`randoms[i]`, or `random.Random(seed)` like the
         reference's `random.random()` per sampling call, sampler.py:351) -- as a launch argument; nothing is read back, so
         the loop stays asynchronous like run().  Rows of a batch share the point through the reference's recurrence.
-        penalties: as capture_sampled; applied on the device ahead of the sampler on either route."""
+        penalties: as capture_sampled; applied on the device ahead of the sampler on either route.  The chain settings (top_a, tfs,
+        typical, temperature_last, smoothing_factor, min_temp, max_temp, temp_exponent, skew, mirostat*, return_top_tokens): as
+        capture_sampled; mu carries over from call to call in `mirostat_mu` like the reference's Settings carry it."""
         import random as _random
+        chain_kw, penalties = self._split_settings(settings)
         ext, cfg = self.model.ext, self.model.config
         if self._overlapped():
             raise RuntimeError("run_sampled: not available on the experimental overlapped chain")
@@ -903,7 +966,9 @@ class GreedyGraphDecoder:
         sm = getattr(self, "_sampled", None)
         pen = self._penalty_state(penalties, old=(sm or {}).get("pen") or getattr(self, "_sample_pen", None))
         self._check_window_known(pen)
+        ch = self._chain_state(chain_kw, temperature, old=(sm or {}).get("chain"))
         if (sm is not None and n_tokens <= sm["randoms"].numel() and pen is sm.get("pen")
+                and (ch or {}).get("key") == (sm.get("chain") or {}).get("key")
                 and (sm["temperature"], sm["top_k"], sm["top_p"], sm["min_p"]) == (float(temperature), int(top_k), float(top_p), float(min_p))):
             # settings of capture_sampled: the sampler is part of the step; the random points travel as ONE copy before the run,
             # then one graph launch per token (eager steps of the same launches where there is no graph)
@@ -941,8 +1006,12 @@ class GreedyGraphDecoder:
                 # the step's own arg-max has written its token to ids / history[:, p0 + i + 1]; the sampled one replaces both
                 # (the position is one ahead already: the penalties' sequence ends at the step's input token)
                 logits = self.logits if pen is None else self._penalised_logits({"pen": pen}, pos_offset=-1)
-                ext.sample_rows(logits, temperature, top_k, top_p, min_p, float(randoms[i]), self.ids, self._sample_probs,
-                                workspace=self._sample_ws, vocab=cfg.vocab_size)
+                if ch is None:
+                    ext.sample_rows(logits, temperature, top_k, top_p, min_p, float(randoms[i]), self.ids, self._sample_probs,
+                                    workspace=self._sample_ws, vocab=cfg.vocab_size)
+                else:
+                    ext.sample_rows_chain(logits, ch["temperature"], top_k, top_p, min_p, float(randoms[i]), self.ids,
+                                          self._sample_probs, workspace=self._sample_ws, vocab=cfg.vocab_size, **ch["kw"])
                 self.history[:, p0 + i + 1].copy_(self.ids)
 
     def tokens(self, start: int, n: int) -> torch.Tensor:

@@ -200,7 +200,14 @@ class SpeculativeGraphDecoder(GreedyGraphDecoder):
         return {"steps": steps, "accepted": accepted, "hist": st[2:2 + self.s], "emitted": steps + accepted,
                 "tokens_per_step": (steps + accepted) / steps if steps else 0.0}
 
-    # capture_sampled: GreedyGraphDecoder's -- capture() above with the sampled tail as the step's last launches
+    # capture_sampled: GreedyGraphDecoder's -- capture() above with the sampled tail as the step's last launches.  The verify step's
+    # sampler is exl2_sample_rows_step2 without the chain stages: this decoder knows none of the chain keywords, so top_a, tfs,
+    # typical, mirostat*, temperature_last, smoothing_factor, min_temp / max_temp / temp_exponent, skew and return_top_tokens are
+    # unknown settings here (TypeError), never silently dropped.
+    CHAIN_DEFAULTS = {}
+
+    def _chain_state(self, kw: dict, temperature: float, old=None):
+        return None
 
     def run_sampled(self, n_steps: int, temperature: float, top_k: int, top_p: float = 0.0, min_p: float = 0.0,
                     randoms=None, seed: int = 0, use_graph: bool = True, **penalties):

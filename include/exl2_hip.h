@@ -542,6 +542,41 @@ int exl2_sample_rows_step2(const void* logits, int logits_f32, int rows, int voc
                            const float* randoms, int n_randoms, const int* counter, int per_row_random,
                            int* out_tokens, float* out_probs, float* workspace,
                            int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream);
+/* The rest of sample_basic's chain (ext_sampling.cpp:153-290) on the device: the settings record the host fills.  A neutral
+   record is all zeros except post_temperature = 1 and temp_exponent = 1; with it the two entries below give what
+   exl2_sample_rows / exl2_sample_rows_step2 give, bit for bit.  Stages, at the reference's positions: smoothing_factor > 0 (the
+   quadratic softmax; row r of a call sees the temperature divided r + 1 times like the reference's batch loop, once with
+   per_row_random), top_a > 0 (between top-p and min-p), 0 < tfs < 1, 0 < typical < 1, mirostat != 0 (mirostat_mu: device fp32
+   [rows], read and written by the launch; 0 = not yet initialised -> 2 tau), post_temperature != 1 or max_temp > min_temp
+   (post-softmax / dynamic temperature), skew != 0, num_probs > 0 (<= 32: the sorted top candidates to out_ktokens int32
+   [rows, num_probs] / out_kprobs fp32 [rows, num_probs], padded with the reference's filler ids and probability 0).  Sorts are
+   descending probability, equal probabilities by ascending token id (the reference's quicksort has no defined order for them).
+   Refused with EXL2_E_UNSUPPORTED: typical together with num_probs > 0 (the pick then depends on the reference's partially sorted
+   buffer).  XTC has no field: xtc_cpu reads stale buffer contents, there is nothing defined to match; the host layers refuse it.
+   One difference from exl2_sample_rows_step2 with a neutral record: with top_k = 1 (or temperature < 0.01) the chain step logs
+   the token to history / advances hist_pos like every other setting does, which exl2_sample_rows_step[2] does not in that branch. */
+typedef struct exl2_sample_chain
+{
+    float top_a, tfs, typical;
+    float post_temperature, min_temp, max_temp, temp_exponent;
+    float smoothing_factor, skew;
+    int   mirostat; float mirostat_tau, mirostat_eta;
+    int   num_probs;
+    float* mirostat_mu;
+    int*   out_ktokens;
+    float* out_kprobs;
+    int*   out_counts;     /* nullable int32 [rows]: the number of candidates the pick was made from */
+} exl2_sample_chain;
+/* exl2_sample_rows with the whole chain. */
+int exl2_sample_rows_chain(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                           float temperature, int top_k, float top_p, float min_p, float random, const exl2_sample_chain* chain,
+                           int* out_tokens, float* out_probs, float* workspace, void* stream);
+/* exl2_sample_rows_step2 with the whole chain: mu and the top tokens live in device memory, so the step replays from one graph. */
+int exl2_sample_rows_chain_step(const void* logits, int logits_f32, int rows, int vocab, int ld, const void* logit_filter,
+                                float temperature, int top_k, float top_p, float min_p,
+                                const float* randoms, int n_randoms, const int* counter, int per_row_random,
+                                const exl2_sample_chain* chain, int* out_tokens, float* out_probs, float* workspace,
+                                int* history, int* hist_pos, int hist_stride, int pos_inc, void* stream);
 /* Repetition / frequency / presence penalties and the token bias of the reference's sampler on the device (csrc/penalties.hip):
    out[row, :] = apply_rep_penalty_cpu (cpp/sampling.cpp:20-110) of float(logits[row, :vocab]), then + token_bias in fp32
    (sampler.py:408-429), bit for bit.  logits [rows, ld] fp16 or fp32 (logits_f32), out fp32 [rows, vocab] (may be the fp32 logits
