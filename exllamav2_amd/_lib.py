@@ -156,6 +156,7 @@ PROTOTYPES = {
     "exl2_chain_overlap_begin": (ci, [vp, ci, vp, vp]),
     "exl2_chain_overlap_end": (ci, [C.POINTER(ci)]),
     "exl2_chain_route_counts": (ci, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), ci]),
+    "exl2_lean_kernel_counts": (ci, [C.POINTER(C.c_uint), C.POINTER(C.c_longlong), ci, ci]),
     "exl2_prefill_route_info": (ci, [C.POINTER(ci)]),
     # speculative greedy decoding (csrc/spec_decode.hip)
     "exl2_spec_accept_draft": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),

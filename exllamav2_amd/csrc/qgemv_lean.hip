@@ -1191,6 +1191,43 @@ static LeanMoeKernelFn lean_moe_kernel(int S, int nslots, bool pair, bool walk)
     }
 }
 
+// which kernel ran: one launch counter per entry of the two lists, bumped where a launch is made (exl2_lean_kernel_counts; plain
+// host integers -- tests account for every instantiation with them).  A grouped-expert kernel's key carries LEAN_KEY_MOE.
+#define LEAN_KEY_MOE (1u << 31)
+struct LeanCount { u32 key; long long n; };
+static LeanCount g_lean_counts[] = {
+#define LEAN_COUNT(G, S, NS, P, OCC, R, W, D, XM, L) { lean_key(G, S, NS, P, R, W, D, XM, L), 0 },
+    LEAN_DENSE_KERNELS(LEAN_COUNT)
+#undef LEAN_COUNT
+#define LEAN_COUNT(S, NS, P, OCC, W) { lean_key(false, S, NS, P, false, W, false, false, false) | LEAN_KEY_MOE, 0 },
+    LEAN_MOE_KERNELS(LEAN_COUNT)
+#undef LEAN_COUNT
+};
+static std::mutex g_lean_counts_mtx;
+static void lean_count(u32 key)
+{
+    std::lock_guard<std::mutex> lock(g_lean_counts_mtx);
+    for (LeanCount& c : g_lean_counts) if (c.key == key) { c.n++; return; }
+}
+
+extern "C" int exl2_lean_kernel_counts(unsigned* keys, long long* counts, int cap, int reset)
+{
+    const int n = (int)(sizeof(g_lean_counts) / sizeof(g_lean_counts[0]));
+    std::lock_guard<std::mutex> lock(g_lean_counts_mtx);
+    for (int i = 0; i < n && i < cap; i++) { if (keys) keys[i] = g_lean_counts[i].key; if (counts) counts[i] = g_lean_counts[i].n; }
+    if (reset) for (LeanCount& c : g_lean_counts) c.n = 0;
+    return n;
+}
+
+// A/B and test switches of the planner: read ONCE per process, unless EXL2_ENV_DYNAMIC is set when the library is first used
+// (modules.hip: ENV_SET -- the tests flip these switches inside one process).  One instantiation, so one stored value, per call site.
+template <typename F> static auto lean_switch(F read) -> decltype(read())
+{
+    static const bool dyn = getenv("EXL2_ENV_DYNAMIC") != nullptr;
+    static const auto v = read();
+    return dyn ? read() : v;
+}
+
 static void lean_attrs()
 {
     static bool attr[EXL2_MAX_DEVICES] = {false};
@@ -1222,7 +1259,7 @@ static int lean_cus()
 int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
 {
     if (in.n_mats < 1 || in.n_mats > FLAT_MAX_MATS || in.M < 1 || in.M > LEAN_MAX_ROWS) return 1;
-    static const int rows_on = []() { const char* e = getenv("EXL2_LEAN_ROWS"); return e ? atoi(e) : 1; }();
+    const int rows_on = lean_switch([]() { const char* e = getenv("EXL2_LEAN_ROWS"); return e ? atoi(e) : 1; });
     bool rows_mode = in.M > LEAN_MAX_M;
     bool rows_loads = false;                                        // the LOADS form (lean_body): one row of a long K, two tiles per workgroup
     if (rows_mode && !rows_on) return 1;
@@ -1259,11 +1296,11 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
     if (const char* e = getenv("EXL2_LEAN_TPW")) { const int v = atoi(e); if (!in.pair && in.n_mats == 1 && (v == 1 || v == 2)) nslots = v; }
     if (const char* e = getenv("EXL2_LEAN_S16")) { if (atoi(e) && nslots == 1 && in.n_mats <= 2) S = 16; }
     const int xmem_on = []() { const char* e = getenv("EXL2_LEAN_XMEM"); return e ? atoi(e) : 1; }();     // (read per launch build: tests switch it)
-    // A/B switches of the candidate lists below (read once)
-    static const int pair4 = []() { const char* e = getenv("EXL2_LEAN_PAIR4"); return e ? atoi(e) : 1; }();
-    static const int pair4_passes = []() { const char* e = getenv("EXL2_LEAN_PAIR4_PASSES"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > LEAN_MAX_PASSES ? LEAN_MAX_PASSES : v); }();
-    static const u32 pair4_budget = []() { const char* e = getenv("EXL2_LEAN_PAIR4_BUDGET_KB"); const int v = e ? atoi(e) : 64; return (u32)(v < 16 ? 16 : (v > 150 ? 150 : v)) * 1024u; }();
-    static const int s8_passes = []() { const char* e = getenv("EXL2_LEAN_S8_PASSES"); const int v = e ? atoi(e) : LEAN_S8_PASSES; return v < 1 ? 1 : (v > LEAN_S8_PASSES ? LEAN_S8_PASSES : v); }();
+    // A/B switches of the candidate lists below (lean_switch: read once)
+    const int pair4 = lean_switch([]() { const char* e = getenv("EXL2_LEAN_PAIR4"); return e ? atoi(e) : 1; });
+    const int pair4_passes = lean_switch([]() { const char* e = getenv("EXL2_LEAN_PAIR4_PASSES"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : (v > LEAN_MAX_PASSES ? LEAN_MAX_PASSES : v); });
+    const u32 pair4_budget = lean_switch([]() { const char* e = getenv("EXL2_LEAN_PAIR4_BUDGET_KB"); const int v = e ? atoi(e) : 64; return (u32)(v < 16 ? 16 : (v > 150 ? 150 : v)) * 1024u; });
+    const int s8_passes = lean_switch([]() { const char* e = getenv("EXL2_LEAN_S8_PASSES"); const int v = e ? atoi(e) : LEAN_S8_PASSES; return v < 1 ? 1 : (v > LEAN_S8_PASSES ? LEAN_S8_PASSES : v); });
     const int s8_single = []() { const char* e = getenv("EXL2_LEAN_S8_SINGLE"); return e ? atoi(e) : 0; }();      // (A/B: the two-load 8-wave form for ONE matrix too -- down_proj)
     const int S0 = S, nslots0 = nslots;
     auto candidates = [&](LeanForm form) {
@@ -1349,7 +1386,7 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
     if (!planned) return 1;
     // one row, one matrix, a 16-wave workgroup per tile and more tiles than CUs (two rounds of workgroups that are alone on their CU):
     // the LOADS form -- two tiles per workgroup over ONE staged copy of the row, one round -- where it plans
-    static const int rows1_on = []() { const char* e = getenv("EXL2_LEAN_ROWS1"); return e ? atoi(e) : 1; }();
+    const int rows1_on = lean_switch([]() { const char* e = getenv("EXL2_LEAN_ROWS1"); return e ? atoi(e) : 1; });
     if (rows1_on && !rows_mode && !xmem && !dep && !in.pair && !in.pair_sum && in.n_mats == 1 && in.M == 1 && S == 16 && !q0->is_gptq && !in.a_tiled && !in.c_tiled && !in.xp_tiled &&
         max_tiles > lean_cus() && !(in.ss_out && (max_tiles + 1) / 2 > LEAN_MAX_PART))
     {
@@ -1386,10 +1423,15 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
 #ifdef EXL2_TRACE
     h.trace = (g_ltrace_buf && g_ltrace_count++ == g_ltrace_which) ? g_ltrace_buf : nullptr;
 #endif
+    // the plan's key: ROWS kernels walk in their two-tile geometries, otherwise only the several-register-loads pair does
+    const bool rows = rows_mode && !xmem;
+    const bool pair_loads = in.pair && S == 4 && planned_passes > 1 && !rows_mode && !xmem && !dep;
+    const bool walk = rows ? nslots == 2 : pair_loads;
+    const u32 key = lean_key(q0->is_gptq, S, nslots, in.pair != 0, rows, walk, dep, xmem, rows_loads);
     if (getenv("EXL2_LEAN_TRACE"))
     {
-        fprintf(stderr, "[lean] M=%d K=%d mats=%d pair=%d S=%d slots=%d wgs=%d lds=%u mode=%d form=%s a_tiled=%d c_tiled=%d\n", in.M, K, in.n_mats, in.pair, S, nslots, wgs, lds,
-                in.a_mode, xmem ? "xmem" : rows_mode ? "rows" : "plain", in.a_tiled, in.c_tiled);
+        fprintf(stderr, "[lean] M=%d K=%d mats=%d pair=%d S=%d slots=%d wgs=%d lds=%u mode=%d form=%s a_tiled=%d c_tiled=%d gptq=%d walk=%d dep=%d loads=%d\n", in.M, K, in.n_mats, in.pair, S, nslots, wgs, lds,
+                in.a_mode, xmem ? "xmem" : rows_mode ? "rows" : "plain", in.a_tiled, in.c_tiled, q0->is_gptq ? 1 : 0, walk ? 1 : 0, dep ? 1 : 0, rows_loads ? 1 : 0);
         for (int j = 0; j < in.n_mats; j++)
             for (int w = 0; w < S; w++)
             {
@@ -1422,12 +1464,10 @@ int qgemv_lean_launch(const FlatIn& in, void* stream, int* wgs_out)
     }
     if (in.plan_only) { if (wgs_out) *wgs_out = wgs; return 0; }                      // a caller asking whether this shape is taken (modules.hip)
     if (getenv("EXL2_LEAN_PLAN_ONLY")) { if (wgs_out) *wgs_out = wgs; return 0; }     // test hook: the host plan without the launch (results undefined)
-    // the plan's key: ROWS kernels walk in their two-tile geometries, otherwise only the several-register-loads pair does
-    const bool rows = rows_mode && !xmem;
-    const bool pair_loads = in.pair && S == 4 && planned_passes > 1 && !rows_mode && !xmem && !dep;
-    const LeanKernelFn kernel = lean_dense_kernel(lean_key(q0->is_gptq, S, nslots, in.pair != 0, rows, rows ? nslots == 2 : pair_loads, dep, xmem, rows_loads));
+    const LeanKernelFn kernel = lean_dense_kernel(key);
     if (!kernel) return 1;                                          // no such instantiation: declined (the caller's fallback runs)
     LAUNCH(kernel, grid, block, lds, stream, a);
+    lean_count(key);
     if (wgs_out) *wgs_out = wgs;
     return 0;
 }
@@ -1536,5 +1576,6 @@ int qgemv_lean_group_launch(const LeanGroupPlan* gp, void* stream, const LeanGro
     const LeanMoeKernelFn kernel = lean_moe_kernel(gp->S, gp->nslots, gp->pair != 0, gp->walk != 0);
     if (!kernel) return 1;
     LAUNCH(kernel, grid, block, gp->lds, stream, table, dyn);
+    lean_count(lean_key(false, gp->S, gp->nslots, gp->pair != 0, false, gp->walk != 0, false, false, false) | LEAN_KEY_MOE);
     return 0;
 }

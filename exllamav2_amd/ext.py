@@ -8,6 +8,7 @@ in the hand-written gfx950 kernels.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import functools
 import os
@@ -28,6 +29,17 @@ def _is_none(t) -> bool:
 # tools/dropin_decode_bench.py -- so the argument checks below read tensor attributes that cost no Python-level object)
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _cur_device = getattr(torch._C, "_cuda_getDevice", None)
+
+
+class LeanKey(collections.namedtuple("LeanKey", "moe gptq S nslots pair rows walk dep xmem loads")):
+    """one kernel of csrc/qgemv_lean.hip: the fields of its entry in LEAN_DENSE_KERNELS / LEAN_MOE_KERNELS (exl2_lean_kernel_counts)"""
+    __slots__ = ()
+
+    @classmethod
+    def decode(cls, key: int) -> "LeanKey":
+        bit = lambda i: bool(key >> i & 1)
+        return cls(moe=bit(31), gptq=bit(16), S=key & 0xFF, nslots=key >> 8 & 0xFF, pair=bit(17), rows=bit(18), walk=bit(19),
+                   dep=bit(20), xmem=bit(21), loads=bit(22))
 
 
 class ExtC:
@@ -993,6 +1005,16 @@ class ExtC:
         a, b = C.c_longlong(0), C.c_longlong(0)
         self.lib.check(self.lib.exl2_chain_route_counts(C.byref(a), C.byref(b), 1 if reset else 0))
         return a.value, b.value
+
+    def lean_kernel_counts(self, reset: bool = False):
+        """{LeanKey: launches since the last reset} with one entry per kernel csrc/qgemv_lean.hip builds (LEAN_DENSE_KERNELS and
+        LEAN_MOE_KERNELS; moe=True marks a grouped-expert kernel)"""
+        n = self.lib.exl2_lean_kernel_counts(None, None, 0, 0)
+        keys, counts = (C.c_uint * n)(), (C.c_longlong * n)()
+        self.lib.exl2_lean_kernel_counts(keys, counts, n, 1 if reset else 0)
+        out = {LeanKey.decode(keys[i]): counts[i] for i in range(n)}
+        assert len(out) == n, "two instantiations with one key"
+        return out
 
     def prefill_route_info(self):
         """(rows, tile rows, weights pre-decoded by wfrag_kernel, calls so far) of the last prefill q_gemm call (>= 129 rows)"""

@@ -470,6 +470,12 @@ int exl2_chain_overlap_begin(void* flags, int n_blocks, void* stream_a, void* st
    the round-2 kernel (csrc/qgemv_flat.hip: what the former declines); reset != 0 zeroes the counters.  Diagnostics for tests and
    bench.py (no reference counterpart). */
 int exl2_chain_route_counts(long long* lean, long long* flat, int reset);
+/* which kernel of csrc/qgemv_lean.hip every lean launch of this process took: one entry per instantiation the library builds
+   (LEAN_DENSE_KERNELS, LEAN_MOE_KERNELS), at most `cap` of them written.  keys[i] = S | nslots << 8 | gptq << 16 | pair << 17 |
+   rows << 18 | walk << 19 | dep << 20 | xmem << 21 | loads << 22, bit 31 set for a grouped-expert kernel; counts[i] = launches
+   since the last reset (plans that launch nothing are not counted).  Returns the number of instantiations (NOT an error code);
+   reset != 0 zeroes the counters.  Diagnostics for tests (no reference counterpart). */
+int exl2_lean_kernel_counts(unsigned* keys, long long* counts, int cap, int reset);
 int exl2_chain_overlap_end(int* n_launches);
 /* which variant of the prefill q_gemm (csrc/qgemm_mfma.hip, >= 129 rows) the LAST call of this process took: out4 = {rows, tile
    rows / 32 (8 = 256-row tile, 4 = 128-row tile), 1 when the weights were decoded once per call by wfrag_kernel / 0 when inside

@@ -223,14 +223,40 @@ def test_chain_decode_many_rows_mixed_groupings(be, recipe, batch, monkeypatch):
     assert calls["n"] > 0
 
 
-def test_llama2_70b_widths_stay_on_the_lean_kernel(be, monkeypatch):
+def _lean_key(S, nslots, gptq=False, pair=False, dep=False):
+    from exllamav2_amd.ext import LeanKey
+    return LeanKey(moe=False, gptq=gptq, S=S, nslots=nslots, pair=pair, rows=False, walk=False, dep=dep, xmem=False, loads=False)
+
+
+def _lean_launches(be):
+    """{kernel of csrc/qgemv_lean.hip: launches} since the last reset (exl2_lean_kernel_counts), the kernels that did not run left out; resets"""
+    return {k: n for k, n in be.ext.lean_kernel_counts(reset=True).items() if n}
+
+
+def _trace_keys(err):
+    """the kernels the planner chose, from the head lines of its trace (EXL2_LEAN_TRACE, printed for plans that launch nothing as well:
+    the emulator plans the wide models without running them)"""
+    from exllamav2_amd.ext import LeanKey
+    keys = []
+    for m in re.finditer(r"\[lean\] M=\d+ K=\d+ mats=\d+ pair=(\d) S=(\d+) slots=(\d) .* form=(\w+) .* gptq=(\d) walk=(\d) dep=(\d) loads=(\d)", err):
+        pair, S, slots, form, gptq, walk, dep, loads = m.groups()
+        keys.append(LeanKey(moe=False, gptq=gptq == "1", S=int(S), nslots=int(slots), pair=pair == "1", rows=form == "rows", walk=walk == "1",
+                            dep=dep == "1", xmem=form == "xmem", loads=loads == "1"))
+    return keys
+
+
+def test_llama2_70b_widths_stay_on_the_lean_kernel(be, monkeypatch, capfd):
     """configs[3]'s shapes (hidden 8192, intermediate 28672, 2.5 bpw: 2 / 3-bit items, 1792-row slices on 16 waves, shares of two
     register passes) through one layer + head of the chained step over a Q4 cache: every launch must be planned by the lean kernel
     -- a host-side limit that declines one of them silently un-chains the WHOLE decoder (it did, for one GPU call of round 4).
-    Emulator: the plans only (EXL2_LEAN_PLAN_ONLY: a 0.9 G-weight layer takes minutes to emulate); GPU: the real launches."""
+    Emulator: the plans only (EXL2_LEAN_PLAN_ONLY: a 0.9 G-weight layer takes minutes to emulate); GPU: the real launches.
+    The kernels of the plan are stated; the same hidden size with intermediate 64 runs against the oracle on both backends in
+    test_gate_up_pair_takes_several_register_loads_on_four_waves, on the same kernels but for down_proj (K = 64 there: the 8-wave
+    kernel; K = 28672 here: the LOADS form, which tests/test_lean_instantiations.py checks at K = 18432)."""
     from exllamav2_amd.config import ExLlamaV2Config
     if be.is_emu:
         monkeypatch.setenv("EXL2_LEAN_PLAN_ONLY", "1")
+    monkeypatch.setenv("EXL2_LEAN_CUS", "256")                      # (the planner's CU count: the emulator and the GPU plan alike)
     cfg = ExLlamaV2Config.llama2_70b(max_seq_len=256, max_input_len=32)
     cfg.num_hidden_layers = 1
     cfg.vocab_size = 512
@@ -240,26 +266,78 @@ def test_llama2_70b_widths_stay_on_the_lean_kernel(be, monkeypatch):
     dec = GreedyGraphDecoder(model, cache, batch_size=1)
     assert dec.chain is not None
     be.ext.chain_route_counts(reset=True)
+    be.ext.lean_kernel_counts(reset=True)
     dec.reset(torch.tensor([3]), 0)
+    capfd.readouterr()
+    monkeypatch.setenv("EXL2_LEAN_TRACE", "1")
     dec.run(1, use_graph=False)
+    monkeypatch.delenv("EXL2_LEAN_TRACE")
     lean, flat = be.ext.chain_route_counts(reset=True)
     assert dec.chain is not None and lean == 5 and flat == 0, (dec.chain is not None, lean, flat)     # q|k|v, o, gate|up, down, head
+    planned = _trace_keys(capfd.readouterr().err)
+    assert planned == [_lean_key(8, 1), _lean_key(8, 1), _lean_key(4, 2, pair=True)._replace(walk=True),
+                       _lean_key(8, 2)._replace(rows=True, walk=True, loads=True), _lean_key(16, 1)], planned
     if not be.is_emu:
+        assert _lean_launches(be) == {k: planned.count(k) for k in planned}
         tok = be.n(dec.tokens(0, 1))
         assert 0 <= int(tok[0, 0]) < cfg.vocab_size
     dec.free(); model.unload()
 
 
+def _rows_key(S, nslots, pair=False):
+    return _lean_key(S, nslots, pair=pair)._replace(rows=True, walk=nslots == 2)
+
+
+# the kernels of a settled step at 8 / 16 sequences, (hidden, intermediate, sequences) -> [q|k|v, o_proj, gate|up, down_proj (every row
+# group: <= 4 rows of a long K on 16 waves), head]; hidden 256: the narrow twins that run against the oracle
+WIDE_INTERMEDIATE_KEYS = {
+    (4096, 14336, 8): [_rows_key(8, 1), _rows_key(8, 1), _rows_key(8, 2, pair=True), _lean_key(16, 1), _rows_key(8, 1)],
+    (4096, 14336, 16): [_rows_key(8, 2), _rows_key(8, 2), _rows_key(8, 2, pair=True), _lean_key(16, 1), _rows_key(8, 2)],
+    (8192, 28672, 8): [_rows_key(16, 1), _rows_key(8, 1), _rows_key(8, 2, pair=True), _lean_key(16, 1), _rows_key(16, 1)],
+    (256, 14336, 8): [_rows_key(8, 1), _rows_key(8, 1), _rows_key(8, 2, pair=True), _lean_key(16, 1), _rows_key(8, 1)],
+    (256, 14336, 16): [_rows_key(8, 2), _rows_key(8, 2), _rows_key(8, 2, pair=True), _lean_key(16, 1), _rows_key(8, 2)],
+    # (K = 256 in place of 8192: q|k|v and the head on 8 waves, not 16; gate|up, and down_proj's long K, as at full width)
+    (256, 28672, 8): [_rows_key(8, 1), _rows_key(8, 1), _rows_key(8, 2, pair=True), _lean_key(16, 1), _rows_key(8, 1)],
+}
+
+
+@pytest.mark.parametrize("inter,recipe,batch,group", [(14336, "4.0bpw", 8, 4), (14336, "4.0bpw", 16, 4), (28672, "2.5bpw", 8, 2)])
+def test_many_rows_at_wide_intermediate_against_oracle(be, monkeypatch, inter, recipe, batch, group):
+    """test_many_rows_at_wide_intermediate_stay_chained's intermediate sizes at hidden 256 (the same long K for down_proj, few columns:
+    what the emulator can run), step by step against the oracle: down_proj is regrouped into rows of `group`, and the kernels launched
+    are those of the full-width step (WIDE_INTERMEDIATE_KEYS; at 28672 but for q|k|v and the head, whose K is 256 here)."""
+    monkeypatch.setenv("EXL2_LEAN_CUS", "256")
+    cfg = tiny_cfg(hidden_size=256, intermediate_size=inter, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1, head_dim=128,
+                   max_batch_size=16)
+    be.ext.lean_kernel_counts(reset=True)
+    be.ext.chain_route_counts(reset=True)
+    _decode_and_check(be, cfg, recipe, batch, steps=2, seed=3)
+    counts = _lean_launches(be)
+    want = WIDE_INTERMEDIATE_KEYS[256, inter, batch]
+    assert set(counts) == set(want), counts
+    if batch == 8 and inter == 14336:
+        assert want == WIDE_INTERMEDIATE_KEYS[4096, inter, batch]
+    # a settled step launches gate|up once and down_proj once per row group (the first step also tries, and is declined, larger groups:
+    # gate|up launches that no down_proj launch follows)
+    steps, rest = divmod(counts[want[3]], -(-batch // group))
+    assert rest == 0 and 2 <= steps <= counts[want[2]], counts
+    lean, flat = be.ext.chain_route_counts(reset=True)
+    assert flat == 0 and lean == sum(counts.values())
+
+
 @pytest.mark.parametrize("hidden,inter,heads,kv,recipe,batch", [(4096, 14336, 32, 8, "4.0bpw", 8), (4096, 14336, 32, 8, "4.0bpw", 16),
                                                                 (8192, 28672, 64, 8, "2.5bpw", 8)])
-def test_many_rows_at_wide_intermediate_stay_chained(be, monkeypatch, hidden, inter, heads, kv, recipe, batch):
+def test_many_rows_at_wide_intermediate_stay_chained(be, monkeypatch, capfd, hidden, inter, heads, kv, recipe, batch):
     """Llama-3-8B / Mistral / Mixtral-dense widths (intermediate 14336) and 70B widths (28672) at 6..16 sequences: down_proj's K is
     beyond the lean kernel's one-pass XMEM form, so the optimistic "all rows in one launch" grouping is declined for that launch
     -- the decoder must regroup (down_proj in row groups of 4) and stay on the chained route, never silently un-chain the whole
-    step (round-4 advisor finding).  Emulator: host plans only; GPU: the real launches, tokens in range."""
+    step (round-4 advisor finding).  Emulator: host plans only; GPU: the real launches, tokens in range.  The kernels of the settled
+    step are WIDE_INTERMEDIATE_KEYS; test_many_rows_at_wide_intermediate_against_oracle runs the same intermediate sizes at hidden 256
+    against the oracle on both backends."""
     from exllamav2_amd.config import ExLlamaV2Config
     if be.is_emu:
         monkeypatch.setenv("EXL2_LEAN_PLAN_ONLY", "1")
+    monkeypatch.setenv("EXL2_LEAN_CUS", "256")                      # (the planner's CU count: the emulator and the GPU plan alike)
     cfg = ExLlamaV2Config(hidden_size=hidden, intermediate_size=inter, num_hidden_layers=1, num_attention_heads=heads,
                           num_key_value_heads=kv, head_dim=128, vocab_size=512, max_seq_len=256, max_input_len=16, max_batch_size=16)
     ck = synth_checkpoint(cfg, be.device, recipe=recipe, seed=0)
@@ -276,9 +354,18 @@ def test_many_rows_at_wide_intermediate_stay_chained(be, monkeypatch, hidden, in
     assert g in (1, 2, 4) and set(dec.chain["group_override"]) == {inter}   # down_proj regrouped, the other launches kept all rows
     assert flat == 0 and lean >= 5, (lean, flat)
     be.ext.chain_route_counts(reset=True)
+    be.ext.lean_kernel_counts(reset=True)
+    capfd.readouterr()
+    monkeypatch.setenv("EXL2_LEAN_TRACE", "1")
     dec.run(1, use_graph=False)                                           # a settled step: q|k|v, o, gate|up, down x groups, head
+    monkeypatch.delenv("EXL2_LEAN_TRACE")
     lean, flat = be.ext.chain_route_counts(reset=True)
     assert (lean, flat) == (4 + -(-batch // g), 0), (lean, flat)
+    planned = _trace_keys(capfd.readouterr().err)
+    want = WIDE_INTERMEDIATE_KEYS[hidden, inter, batch]
+    assert len(planned) == lean and planned[:3] == want[:3] and planned[-1] == want[-1] and set(planned[3:-1]) == {want[3]}, planned
+    if not be.is_emu:
+        assert _lean_launches(be) == {k: planned.count(k) for k in planned}
     if not be.is_emu:
         tok = be.n(dec.tokens(0, 2))
         assert tok.min() >= 0 and tok.max() < cfg.vocab_size
@@ -320,14 +407,47 @@ def test_chain_tokens_equal_unchained_route(be, monkeypatch):
     assert (outs[0][0] == outs[1][0]).mean() >= 0.8
 
 
-@pytest.mark.parametrize("recipe,batch", [("4.0bpw", 1), ("3.5bpw", 3), ("gptq-4bit-128g", 2)])
+# The DEP kernels of csrc/qgemv_lean.hip (the launches of an overlapped chain) and the fewest one-layer decoders that reach them all:
+# (recipe, sequences, hooks) -> the kernels of one step.  q|k|v is three matrices on 8 waves per tile in every one; one sequence: the
+# 4-wave tile pair for gate|up, 16 waves for o / down / head where forced; three sequences: the 8-wave pair, two tiles per workgroup
+# for o / down / head where forced.  tests/test_lean_instantiations.py counts these keys as covered here.
+OVERLAP_CASES = {
+    "exl2-1-s16": ("3.5bpw", 1, {"EXL2_LEAN_S16": "1"}, False),
+    "exl2-3-tpw2": ("2.5bpw", 3, {"EXL2_LEAN_TPW": "2"}, False),
+    "gptq-1-s16": ("gptq-4bit-32g", 1, {"EXL2_LEAN_S16": "1"}, True),
+    "gptq-3-tpw2": ("gptq-4bit-128g", 3, {"EXL2_LEAN_TPW": "2"}, True),
+}
+OVERLAP_STEPS = {
+    name: ({_lean_key(8, 1, g, dep=True): 1, _lean_key(16, 1, g, dep=True): 3, _lean_key(4, 2, g, pair=True, dep=True): 1} if seqs == 1 else
+           {_lean_key(8, 1, g, dep=True): 1, _lean_key(8, 2, g, dep=True): 3, _lean_key(8, 2, g, pair=True, dep=True): 1})
+    for name, (_, seqs, _, g) in OVERLAP_CASES.items()}
+OVERLAP_KEYS = sorted({k for step in OVERLAP_STEPS.values() for k in step})
+
+
+@pytest.mark.parametrize("recipe,batch", [("4.0bpw", 1), ("3.5bpw", 3), ("gptq-4bit-128g", 2)] + [(name, 0) for name in OVERLAP_CASES],
+                         ids=["4.0bpw-1", "3.5bpw-3", "gptq-4bit-128g-2"] + list(OVERLAP_CASES))
 def test_overlapped_chain_equals_serial_chain(be, monkeypatch, recipe, batch):
     """EXL2_CHAIN_OVERLAP=1 (csrc/chain_sync.h): the same launches of the lean kernel on two alternating streams, dependencies
     through words in memory, a gate kernel ahead of every launch.  Same arithmetic, same order of every sum (the pipelined
     form of the serial chain changes WHEN an item is decoded, not the order of the sums): logits and tokens are bit-identical to
     the one-stream chain -- on the GPU through two captured graphs (one per stream) replayed side by side for several steps;
-    the hand-off words (counters, shards, entry counts, "go") are back to zero after every step and no wait gave up."""
+    the hand-off words (counters, shards, entry counts, "go") are back to zero after every step and no wait gave up.
+
+    OVERLAP_CASES: one-layer decoders that between them launch every DEP kernel the library builds -- the overlapped run's launches are
+    the case's kernels and no others (exl2_lean_kernel_counts), the serial run of the same model is checked against the oracle step by
+    step (_decode_and_check), and the overlapped run is bit-identical to the serial one as above."""
     cfg = tiny_cfg(num_hidden_layers=3, num_attention_heads=4, num_key_value_heads=2, intermediate_size=384)
+    step = None
+    if recipe in OVERLAP_CASES:
+        step = OVERLAP_STEPS[recipe]
+        recipe, batch, env, _ = OVERLAP_CASES[recipe]
+        # (K = 1024 in every launch: 8 items per tile, a share for every wave)
+        cfg = tiny_cfg(num_hidden_layers=1, hidden_size=1024, intermediate_size=1024, num_attention_heads=8, num_key_value_heads=2, head_dim=128)
+        monkeypatch.setenv("EXL2_LEAN_CUS", "256")                        # (the planner's CU count: the emulator and the GPU plan alike)
+        for name, v in env.items():
+            monkeypatch.setenv(name, v)
+        monkeypatch.setenv("EXL2_CHAIN_OVERLAP", "0")
+        _decode_and_check(be, cfg, recipe, batch, steps=2, seed=21, act_order=not recipe.startswith("gptq"))
     outs = []
     for overlap in ("0", "1"):
         monkeypatch.setenv("EXL2_CHAIN_OVERLAP", overlap)
@@ -336,6 +456,7 @@ def test_overlapped_chain_equals_serial_chain(be, monkeypatch, recipe, batch):
         cache = ExLlamaV2Cache(model, batch_size=batch)
         dec = GreedyGraphDecoder(model, cache, batch_size=batch)
         assert dec.chain is not None and ("flags" in dec.chain) == (overlap == "1")
+        be.ext.lean_kernel_counts(reset=True)
         if not be.is_emu:
             dec.capture()
         dec.reset(torch.arange(batch) + 5, 0)
@@ -360,6 +481,9 @@ def test_overlapped_chain_equals_serial_chain(be, monkeypatch, recipe, batch):
                 warnings.warn(f"overlapped chain: {gave_up} waits gave up (the two graphs did not run side by side)")
             assert np.all(flags == 0), np.nonzero(flags)
             assert sum(be.ext.chain_route_counts()) > 0
+            if step is not None:                                          # every launch a DEP kernel of the case, in a step's proportions
+                counts = {k: n for k, n in be.ext.lean_kernel_counts(reset=True).items() if n}
+                assert set(counts) == set(step) and len({counts[k] / step[k] for k in step}) == 1, counts
         dec.free(); model.unload()
     assert np.array_equal(outs[0][0], outs[1][0])
     assert np.array_equal(outs[0][1], outs[1][1])
@@ -583,11 +707,14 @@ def test_gemm_chain_shares_of_several_register_loads(be, rows, spec_name, capfd,
     ss = (x.astype(np.float32) ** 2).sum(-1, keepdims=True).astype(np.float32)
     c = torch.zeros((rows, n), dtype=torch.float16, device=be.device)
     be.ext.chain_route_counts(reset=True)                              # (process-wide: not the launches of whatever ran before)
+    be.ext.lean_kernel_counts(reset=True)
     monkeypatch.setenv("EXL2_LEAN_TRACE", "1")
+    monkeypatch.setenv("EXL2_LEAN_CUS", "256")                         # (one row: not the LOADS form, whatever the CU count here)
     be.ext.gemm_half_q_half_chain(be.t(xp), be.t(ss), 1, 1e-5, h, c, rows)
     monkeypatch.delenv("EXL2_LEAN_TRACE")
     err = capfd.readouterr().err
     assert " S=16 " in err, err[:400]
+    assert set(_lean_launches(be)) == {_lean_key(16, 1)}
     depth = {2: 10, 3: 8, 4: 6}
     shares = [(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"; (\d+) x (\d+)b", err)]
     assert any(cnt > depth[bits] for cnt, bits in shares), shares
@@ -626,11 +753,15 @@ def test_gemm_chain_one_row_two_tiles_per_workgroup(be, spec_name, capfd, monkey
     monkeypatch.setenv("EXL2_LEAN_CUS", "2")
     monkeypatch.setenv("EXL2_LEAN_TRACE", "1")
     be.ext.chain_route_counts(reset=True)
+    be.ext.lean_kernel_counts(reset=True)
     be.ext.gemm_half_q_half_chain(be.t(xp), be.t(ss), 1, 1e-5, h, c, 1)
     monkeypatch.delenv("EXL2_LEAN_TRACE")
     err = capfd.readouterr().err
     head = [l for l in err.split("\n") if l.startswith("[lean] M=1 ")]
     assert head and " S=8 slots=2 wgs=3 " in head[0] and "form=rows" in head[0], head[:2]
+    assert " gptq=0 walk=1 dep=0 loads=1" in head[0], head[0]
+    loads_key = _lean_key(8, 2)._replace(rows=True, walk=True, loads=True)
+    assert _lean_launches(be) == {loads_key: 1}
     depth = {2: 10, 3: 8, 4: 6, 5: 5}
     shares = [(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"; (\d+) x (\d+)b", err)]
     assert any(cnt > 2 * depth[bits] for cnt, bits in shares), shares          # (three register loads at least)
@@ -640,6 +771,7 @@ def test_gemm_chain_one_row_two_tiles_per_workgroup(be, spec_name, capfd, monkey
     monkeypatch.setenv("EXL2_LEAN_ROWS1", "0")                                # (the plain form: same sums within the same bar)
     c2 = torch.zeros((1, n), dtype=torch.float16, device=be.device)
     be.ext.gemm_half_q_half_chain(be.t(xp), be.t(ss), 1, 1e-5, h, c2, 1)
+    assert _lean_launches(be) == {_lean_key(16, 1): 1}                        # (the switch is re-read: the plain 16-wave kernel, not LOADS again)
     assert np.all(np.abs(be.n(c2).astype(np.float64) - want) <= slack * half_tol(want, k))
     lean, flat = be.ext.chain_route_counts(reset=True)
     assert flat == 0 and lean == 2
@@ -688,12 +820,17 @@ def test_qkv_launch_takes_two_register_loads_on_eight_waves(be, capfd, monkeypat
     cfg = tiny_cfg(hidden_size=8192, intermediate_size=256, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1,
                    head_dim=128)
     monkeypatch.setenv("EXL2_LEAN_TRACE", "1")
+    monkeypatch.setenv("EXL2_LEAN_CUS", "256")                     # (the planner's CU count: the emulator and the GPU plan alike)
+    be.ext.lean_kernel_counts(reset=True)
     _decode_and_check(be, cfg, "2.5bpw", 1, steps=2, seed=5)
     monkeypatch.delenv("EXL2_LEAN_TRACE")
     err = capfd.readouterr().err
     blocks = err.split("[lean] M=")
     qkv = [b for b in blocks if b.startswith("1 K=8192 mats=3 ")]
     assert qkv and all(" S=8 " in b.split("\n")[0] for b in qkv), [b.split("\n")[0] for b in blocks][:8]
+    # q|k|v, o_proj and down_proj on the 8-wave kernel, the head (K = 8192, 6 bits) on 16 waves, gate|up (K = 8192, intermediate 256) as it plans
+    counts = _lean_launches(be)
+    assert counts.get(_lean_key(8, 1), 0) >= 3 and counts[_lean_key(8, 1)] == 3 * counts.get(_lean_key(16, 1), 0), counts
     depth = {2: 10, 3: 8, 4: 6}
     shares = [(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"; (\d+) x (\d+)b", qkv[0])]
     assert any(cnt > depth.get(bits, 99) for cnt, bits in shares), shares
@@ -708,6 +845,8 @@ def test_gate_up_pair_takes_several_register_loads_on_four_waves(be, capfd, monk
     cfg = tiny_cfg(hidden_size=8192, intermediate_size=64, num_hidden_layers=1, num_attention_heads=2, num_key_value_heads=1,
                    head_dim=128)
     monkeypatch.setenv("EXL2_LEAN_TRACE", "1")
+    monkeypatch.setenv("EXL2_LEAN_CUS", "256")                     # (the planner's CU count: the emulator and the GPU plan alike)
+    be.ext.lean_kernel_counts(reset=True)
     _decode_and_check(be, cfg, "2.5bpw", 1, steps=2, seed=5)
     monkeypatch.delenv("EXL2_LEAN_TRACE")
     err = capfd.readouterr().err
@@ -717,6 +856,14 @@ def test_gate_up_pair_takes_several_register_loads_on_four_waves(be, capfd, monk
     depth = {2: 10, 3: 8, 4: 6}
     shares = [(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"; (\d+) x (\d+)b", gu[0])]
     assert any(cnt > depth.get(bits, 99) for cnt, bits in shares), shares
+    pair_loads, pair_16 = _lean_key(4, 2, pair=True)._replace(walk=True), _lean_key(8, 2, pair=True)
+    counts = _lean_launches(be)
+    assert counts.get(pair_loads, 0) >= 2 and pair_16 not in counts, counts
+    # the former plan (one register load per wave: 8 waves per tile, the 16-wave workgroup): same logits within the same bar
+    monkeypatch.setenv("EXL2_LEAN_PAIR4_PASSES", "1")
+    _decode_and_check(be, cfg, "2.5bpw", 1, steps=2, seed=5)
+    counts = _lean_launches(be)
+    assert counts.get(pair_16, 0) >= 2 and pair_loads not in counts, counts
 
 
 @pytest.mark.parametrize("spec_id", ["5_4", "3_2_pairs"])
